@@ -1,8 +1,22 @@
 #!/usr/bin/env python3
 """Decode benchmark: Llama-2-7B fp16 single-stream greedy decode to 2048 tokens.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
+
+A plain run does only what `value` needs: it builds the engine, runs W warmup
+steps, times K steps, writes the last step's outputs if `--dump-outputs` is
+given, and prints one JSON line (`value`, `ms_per_step`, the decode loop's
+algorithmic HBM fraction). Everything else described below -- the per-kernel and
+roofline timings, the measured HBM read peak, the TP exchange, graph timeline,
+prefill and int8 side measurements and the CPU baseline -- runs only with `--full`.
+
+`--dump-outputs DIR` writes what a caller of the timed path receives after the
+last timed step as DIR/<name>.npy: `tokens` (prompt + generated ids, float64),
+`logits` (the last forward's logits, float32; this rank's vocabulary shard at
+N > 1) and `hidden` (the last forward's final hidden state, float32). Ranks other
+than 0 write <name>_rank<r>.npy. Weights and prompt come from a fixed seed, so
+the same arguments give the same inputs in every run and on every build.
 
 One "step" = one full greedy generation on the BASELINE.json configs[1]
 workload: synthetic random-init Llama-2-7B weights (llmi-prng-v1, fp16), an
@@ -15,7 +29,7 @@ run, else RCCL all-reduce); each rank streams 1/N of the weights, total work is
 fixed ("strong" scaling). Started without a launcher, `--gpus N` spawns the N
 rank processes itself (before any GPU call).
 
-value = generated tokens / s (whole job). Also reported: HBM roofline of the
+value = generated tokens / s (whole job). Also reported with `--full`: HBM roofline of the
 dominant kernel (gate_up GEMV, HIP events on the engine stream, launches cycling
 through the 32 layers so the weights stream from HBM as in the loop), the whole
 decode loop's algorithmic HBM fraction, and a CPU baseline (the numpy oracle,
@@ -383,6 +397,19 @@ def tp_exchange_side(eng, layers, ms_per_token, wbytes, mode="rccl", rccl=True):
     return out
 
 
+def dump_outputs(dirname: str, eng, toks, rank: int):
+    """--dump-outputs: the timed path's results after its last step, as a caller reads them
+    back from the engine -- the whole token sequence, the last forward's logits (this rank's
+    vocabulary shard) and its final hidden state. A few hundred KB in all."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = "" if rank == 0 else f"_rank{rank}"
+    arrays = {"tokens": np.asarray(toks, np.float64), "logits": eng.logits().astype(np.float32),
+              "hidden": eng.hidden().astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def spawn_workers(n: int, argv) -> int:
     """`--gpus N` (N > 1) started without a launcher: start N workers of this script,
     one per GPU (RANK = LOCAL_RANK = r, WORLD_SIZE = N, rendezvous on 127.0.0.1), and
@@ -444,12 +471,20 @@ def main():
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--max-seq", type=int, default=MAX_SEQ)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the prefill / int8-13B side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel / roofline timings, the measured HBM read "
+                         "peak, the side measurements (TP exchange, graph timeline, prefill, int8 13B) and the CPU "
+                         "baseline; a plain run stops at the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's tokens, logits and hidden state as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-side", action="store_true",
+                    help="with --full: skip the graph timeline / prefill / int8-13B side measurements")
     ap.add_argument("--kv", choices=["f16", "f32"], default="f16")
     ap.add_argument("--tp-exchange", action="store_true",
                     help="world 1: give the engine a single-rank RCCL communicator (its all-reduces run in the "
-                         "decode graph) and time the TP exchange -- a rehearsal of the world > 1 side measurement")
+                         "decode graph) and, with --full, time the TP exchange -- a rehearsal of the world > 1 side "
+                         "measurement")
     ap.add_argument("--eager", action="store_true",
                     help="launch kernels eagerly instead of replaying the hipGraph (profiling: rocprofv3 "
                          "kernel tracing of graph replays crashes on ROCm 7.2)")
@@ -538,42 +573,45 @@ def main():
         consistent = all(o == objs[0] for o in objs)
 
     wbytes, kvb = eng.bytes_per_token()
-    progress("kernel timings")
-    # dominant kernel: gate_up GEMV, timed with HIP events on the engine stream
-    gu_us, gu_bytes = eng.time_kernel("gate_up", iters=256)
-    kern = {k: eng.time_kernel(k, iters=128) for k in ("qkv", "attn", "o", "down", "lm_head")}
-    try:  # the decode graph's q/k/v + attention launch (the two kernels above, fused)
-        kern["qkv_attn"] = eng.time_kernel("qkv_attn", iters=128)
-    except Exception as e:  # reported, never fatal to the GPU number
-        progress(f"qkv_attn timing skipped: {e!r}"[:200])
-    try:
-        peak_meas = hbm_read_peak(gu_bytes)
-    except Exception as e:  # reported, never fatal to the GPU number
-        peak_meas = {"error": repr(e)[:300]}
-    side = {}
-    if tp_id is not None or one_dev:
-        progress("tp exchange side measurement")
-        try:
-            side["tp_exchange"] = tp_exchange_side(eng, cfg.layers, elapsed * 1e3 / args.steps / n_fwd, wbytes,
-                                                   mode=xchg["mode"], rccl=tp_id is not None)
-            if one_dev:
-                side["tp_exchange"]["one_device_rehearsal"] = True
-            for k in ("oneshot_rejected", "fused_rejected", "us_per_forward_oneshot_vs_fused"):
-                if k in xchg:
-                    side["tp_exchange"][k] = xchg[k]
+    dumped = dump_outputs(args.dump_outputs, eng, toks, rank) if args.dump_outputs else None
+    gu_us = gu_bytes = None
+    kern, peak_meas, side = {}, {}, {}
+    if args.full:
+        progress("kernel timings")
+        # dominant kernel: gate_up GEMV, timed with HIP events on the engine stream
+        gu_us, gu_bytes = eng.time_kernel("gate_up", iters=256)
+        kern = {k: eng.time_kernel(k, iters=128) for k in ("qkv", "attn", "o", "down", "lm_head")}
+        try:  # the decode graph's q/k/v + attention launch (the two kernels above, fused)
+            kern["qkv_attn"] = eng.time_kernel("qkv_attn", iters=128)
         except Exception as e:  # reported, never fatal to the GPU number
-            side["tp_exchange"] = {"error": repr(e)[:300]}
-    if world == 1 and not args.no_side and not args.eager:
-        progress("graph timeline side measurement")
+            progress(f"qkv_attn timing skipped: {e!r}"[:200])
         try:
-            side["graph_timeline"] = graph_timeline_side(eng, prompt)
+            peak_meas = hbm_read_peak(gu_bytes)
         except Exception as e:  # reported, never fatal to the GPU number
-            side["graph_timeline"] = {"error": repr(e)[:300]}
-    if world == 1 and not args.no_side:
-        progress("prefill side measurement")
-        side["prefill"] = prefill_side(eng, prompt_len=512)
+            peak_meas = {"error": repr(e)[:300]}
+        if tp_id is not None or one_dev:
+            progress("tp exchange side measurement")
+            try:
+                side["tp_exchange"] = tp_exchange_side(eng, cfg.layers, elapsed * 1e3 / args.steps / n_fwd, wbytes,
+                                                       mode=xchg["mode"], rccl=tp_id is not None)
+                if one_dev:
+                    side["tp_exchange"]["one_device_rehearsal"] = True
+                for k in ("oneshot_rejected", "fused_rejected", "us_per_forward_oneshot_vs_fused"):
+                    if k in xchg:
+                        side["tp_exchange"][k] = xchg[k]
+            except Exception as e:  # reported, never fatal to the GPU number
+                side["tp_exchange"] = {"error": repr(e)[:300]}
+        if world == 1 and not args.no_side and not args.eager:
+            progress("graph timeline side measurement")
+            try:
+                side["graph_timeline"] = graph_timeline_side(eng, prompt)
+            except Exception as e:  # reported, never fatal to the GPU number
+                side["graph_timeline"] = {"error": repr(e)[:300]}
+        if world == 1 and not args.no_side:
+            progress("prefill side measurement")
+            side["prefill"] = prefill_side(eng, prompt_len=512)
     eng.close()
-    if world == 1 and not args.no_side:
+    if args.full and world == 1 and not args.no_side:
         progress("int8 13B side measurement")
         side["int8_13b"] = int8_side()
     if rank != 0:
@@ -583,8 +621,25 @@ def main():
     value = gen_per_step * args.steps / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
     per_rank_bytes = algorithmic_bytes(wbytes, kvb, n_fwd)
-    traffic, traffic_src = pmc_traffic("gate_up")
-    achieved = gu_bytes / (gu_us * 1e-6) / 1e9
+    full = {}
+    if args.full:  # what the per-kernel timings and the measured read peak feed
+        traffic, traffic_src = pmc_traffic("gate_up")
+        achieved = gu_bytes / (gu_us * 1e-6) / 1e9
+        full["roofline"] = {
+            "bound": "hbm", "kernel": "gate_up GEMV (rmsnorm+gate_up+silu*mul), layers cycled",
+            "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+            "algorithmic_bytes": gu_bytes, "avg_us": round(gu_us, 2),
+            "traffic_source": traffic_src,
+            # the headline frac is against the 8 TB/s spec (peak); peak_measured is a
+            # one-shot HBM read of the same bytes in this process (and a 1 GiB read)
+            "denominator": "peak = 8 TB/s spec (headline); frac_of_measured uses peak_measured.same_bytes",
+            "peak_measured": peak_meas,
+            "frac_of_measured": (round(achieved / peak_meas["same_bytes"]["GBps"], 4)
+                                 if "same_bytes" in peak_meas else None)}
+        full["kernels_us"] = {"gate_up": round(gu_us, 2), **{k: round(v[0], 2) for k, v in kern.items()}}
+        full["kernels_GBps"] = {"gate_up": round(achieved, 1),
+                                **{k: round(v[1] / (v[0] * 1e-6) / 1e9, 1) for k, v in kern.items()}}
     out = {
         "metric": "decode tokens/sec Llama-2-7B fp16 @1 GPU; % HBM roofline; 1->8 TP curve",
         "value": round(value, 2),
@@ -604,17 +659,7 @@ def main():
                    "generated_per_step": gen_per_step, "kv_cache": args.kv,
                    "weights": "fp16, fp32 activations/accumulate",
                    "parallelism": f"tp{world}" if world > 1 else "single"},
-        "roofline": {"bound": "hbm", "kernel": "gate_up GEMV (rmsnorm+gate_up+silu*mul), layers cycled",
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                     "algorithmic_bytes": gu_bytes, "avg_us": round(gu_us, 2),
-                     "traffic_source": traffic_src,
-                     # the headline frac is against the 8 TB/s spec (peak); peak_measured is a
-                     # one-shot HBM read of the same bytes in this process (and a 1 GiB read)
-                     "denominator": "peak = 8 TB/s spec (headline); frac_of_measured uses peak_measured.same_bytes",
-                     "peak_measured": peak_meas,
-                     "frac_of_measured": (round(achieved / peak_meas["same_bytes"]["GBps"], 4)
-                                          if "same_bytes" in peak_meas else None)},
+        "full": args.full,
         "decode_loop_hbm": {"bytes_per_step_per_rank": per_rank_bytes,
                             "achieved_GBps_per_rank": round(per_rank_bytes / (elapsed / args.steps) / 1e9, 1),
                             "frac_of_8TBps": round(per_rank_bytes / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 4),
@@ -623,13 +668,13 @@ def main():
                                       peak_meas["sustained_1GiB"]["GBps"], 4)
                                 if "sustained_1GiB" in peak_meas else None),
                             "weight_bytes_per_token": wbytes, "kv_bytes_per_pos": kvb},
-        "kernels_us": {"gate_up": round(gu_us, 2), **{k: round(v[0], 2) for k, v in kern.items()}},
-        "kernels_GBps": {"gate_up": round(achieved, 1),
-                         **{k: round(v[1] / (v[0] * 1e-6) / 1e9, 1) for k, v in kern.items()}},
+        **full,
         "tp_tokens_consistent": consistent,
         **side,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             progress("cpu baseline")
             out["cpu_baseline"] = cpu_baseline()

@@ -35,6 +35,12 @@ def test_single_gpu_dry_run_needs_no_spawn():
     assert json.loads(r.stdout.strip())["n_gpus"] == 1
 
 
+def test_full_and_dump_outputs_options_exist(tmp_path):
+    r = _run(["--dry-run", "--full", "--dump-outputs", str(tmp_path / "dump")])
+    assert r.returncode == 0, r.stderr
+    assert json.loads(r.stdout.strip())["dry_run"]
+
+
 def test_launcher_mismatch_is_an_error():
     r = _run(["--gpus", "2", "--dry-run"], env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0

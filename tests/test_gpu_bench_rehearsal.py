@@ -22,7 +22,7 @@ def test_bench_two_ranks_one_device_oneshot():
     env = dict(os.environ, LLMI_BENCH_ONE_DEVICE="1")
     env.pop("WORLD_SIZE", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--max-seq", "128", "--steps", "1",
-           "--warmup", "0", "--no-side", "--no-cpu-baseline"]
+           "--warmup", "0", "--full", "--no-side", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -4,7 +4,7 @@
 # Steps, run in order; the first failure ends the call (nothing more touches the GPU):
 #   pytest            the whole GPU suite              pytest=<args>  e.g. pytest=tests/test_gpu_ring.py
 #   smoke             __graft_entry__.smoke()
-#   bench             bench.py (BENCH_ARGS env: extra flags)
+#   bench             bench.py --full (BENCH_ARGS env: extra flags)
 #   trace             rocprofv3 kernel trace of one eager bench step (+ tools/trace_summary.py)
 #   pmc               FETCH_SIZE and WRITE_SIZE passes (separate runs) on the decode kernels
 #   pftrace           rocprofv3 kernel trace of a 512-row prefill (PF_MODE env: exact | exact8 | fast, default exact8)
@@ -38,14 +38,14 @@ for s in "$@"; do
       tail -1 $OUT/smoke_$TAG.log ;;
     bench)
       step "bench ${BENCH_ARGS:-}"
-      timeout -k 10 900 python -u bench.py ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err \
+      timeout -k 10 900 python -u bench.py --full ${BENCH_ARGS:-} > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err \
         || fail $? bench $OUT/bench_$TAG.err
       cat $OUT/bench_$TAG.json ;;
     trace)
       step "kernel trace (eager bench step)"
       rm -rf /tmp/prof_trace
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d /tmp/prof_trace -o trace --output-format csv -- \
-        python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-side --eager > $OUT/trace_$TAG.log 2>&1 \
+        python3 bench.py --steps 1 --warmup 0 --eager > $OUT/trace_$TAG.log 2>&1 \
         || fail $? trace $OUT/trace_$TAG.log
       find /tmp/prof_trace -name '*kernel_stats.csv' -exec cp {} $OUT/kernel_stats_$TAG.csv \;
       python3 tools/trace_summary.py $(find /tmp/prof_trace -name '*kernel_trace.csv' | head -1) \
