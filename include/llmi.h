@@ -150,6 +150,95 @@ int llmi_stream_errors(llmi_stream_t stream, int* flags);
  * must still be correct: flags carry a per-launch epoch). 0 / launches 0 clears it. */
 int llmi_debug_stream_k(int mode, int launches);
 
+/* Test hooks for the decode engine's kernel forms (no reference counterpart; test-only: no
+ * engine or operator path calls them). The operator calls above reach the GEMV only with an
+ * fp32 x and the store / add / silu epilogues, and the decode attention only with its merge
+ * kernel; a decoded token runs other forms of both. These hooks launch those forms directly.
+ *
+ * llmi_debug_gemv: every field is copied into the launcher's argument block as it stands and
+ * the GEMV is launched once on `stream`. Zero (NULL) means "not used"; the only defaults are
+ * eps 0 -> 1e-5 and ksplit 0 -> 1. w_dtype / g_dtype are llmi_dtype values. The caller owns
+ * every buffer (device memory).
+ *   w [n_rows, ldw (0: k)] with per-row fp16 `scales` for int8; x fp32 [k], or x_fixed int64
+ *   [k] (value * 2^32) with RMSNorm, whose fp32 image workgroup 0 writes to x_out;
+ *   gamma non-NULL: RMSNorm of x (gamma dtype g_dtype: f16 / f32) folded in;
+ *   epi 0: y[r] = acc; 1: y[r] = acc + resid_scale * resid[r] (resid may alias y);
+ *       2: y[g] = silu(acc[g]) * acc[g + pair_off] (n_rows = 2 pair_off);
+ *       3: y[r] = acc, and workgroup b's best key (value bits << 32 | 0xFFFFFFFF - (idx_base + r))
+ *          in partials[b];
+ *       4: yacc[r] += fixed(acc) (int64, value * 2^32) with K split over ksplit workgroups; or,
+ *          with yacc_single (ksplit 1), yacc[r] = yacc_base[r] (NULL: 0) + fixed(acc) stored,
+ *          and the same value in yacc_copy[r] when given;
+ *   grid > 0: that many workgroups (waves loop over row groups); kpar 2 / 4: K split over the
+ *   waves of a workgroup (store / silu, RMSNorm, x_fixed, automatic grid);
+ *   seed_dst non-NULL: seed_dst[0, seed_n) = seed_keep ? seed_src : 0 on the side.
+ * llmi_debug_gemv_plan launches nothing: it checks the same arguments and reports the grid,
+ * the unroll (16-B loads per row in flight: 4, 5 or 8) and the x-staging width (float4s of x
+ * per thread: 4, 5, 11, 14, or 0 for the strided form) that llmi_debug_gemv will use. */
+typedef struct llmi_debug_gemv_args {
+    const void* w;
+    const void* scales;
+    int w_dtype, n_rows, k, ldw;
+    const float* x;
+    const long long* x_fixed;
+    float* x_out;
+    const void* gamma;
+    int g_dtype;
+    float eps;
+    int epi;
+    float* y;
+    const float* resid;
+    float resid_scale;
+    int pair_off;
+    unsigned long long* partials;
+    uint32_t idx_base;
+    int grid;
+    int ksplit;
+    long long* yacc;
+    int yacc_single;
+    const long long* yacc_base;
+    long long* yacc_copy;
+    const long long* seed_src;
+    long long* seed_dst;
+    int seed_n, seed_keep;
+    int kpar;
+} llmi_debug_gemv_args;
+int llmi_debug_gemv(const llmi_debug_gemv_args* args, llmi_stream_t stream);
+int llmi_debug_gemv_plan(const llmi_debug_gemv_args* args, int* grid, int* unroll, int* xpt);
+
+/* llmi_debug_attn_oproj: one layer's decode attention as the engine's separate launches run
+ * it -- the split-KV attention leaving its partials in `workspace` (no merge kernel), then the
+ * o_proj that merges them by head and adds W_o . o into xacc[n_rows] (int64, value * 2^32)
+ * with fixed-point atomics. The attention launch first seeds xacc: resid_scale 0 -> zeros,
+ * else resid_fixed (int64) when given, else fixed(resid). Position: the device int *pos_dev;
+ * nact > 0 must be *pos_dev / 64 + 1 (the grid holds only the active splits; a mismatch sets
+ * bit 4 in *err and computes nothing), nact 0 sizes the grid for max_seq. k_cache / v_cache:
+ * one layer [kv_heads, max_seq, head_dim] of cache_dtype; slot *pos_dev is written. w: W_o
+ * [n_rows, ldw] (ldw >= heads * head_dim: a column shard of a wider matrix), or head_major
+ * [heads][n_rows][head_dim]; per-row fp16 `scales` for int8. head_dim 0 -> 128, rope_base
+ * 0 -> 10000. The caller owns every buffer, `workspace` (llmi_attn_workspace_bytes) included. */
+typedef struct llmi_debug_attn_oproj_args {
+    const float* qkv;
+    void* k_cache;
+    void* v_cache;
+    int cache_dtype, max_seq;
+    const int* pos_dev;
+    int nact;
+    int heads, kv_heads, head_dim;
+    int rope;
+    float rope_base;
+    void* workspace;
+    long long* xacc;
+    const float* resid;
+    const long long* resid_fixed;
+    float resid_scale;
+    const void* w;
+    const void* scales;
+    int w_dtype, head_major, n_rows, ldw;
+    int* err;
+} llmi_debug_attn_oproj_args;
+int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t stream);
+
 /* Diagnostics (no reference counterpart): while `stamps` (device memory, 8 u64 per
  * workgroup) is non-null, every launch of the transposed prefill attention kernel writes its
  * per-workgroup timeline there (WgStamp: start, copies of the first block landed, loop end,

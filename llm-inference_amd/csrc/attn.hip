@@ -198,6 +198,7 @@ int attn_oproj_launch(const OprojArgs& a, hipStream_t s) {
     LLMI_REQUIRE(a.head_dim == D, "attn_oproj: head_dim must be 128");
     LLMI_REQUIRE(a.w && a.workspace && a.xacc && a.heads > 0 && a.n_rows > 0, "attn_oproj: bad arguments");
     LLMI_REQUIRE(a.ldw >= a.heads * D, "attn_oproj: ldw < heads * head_dim");
+    LLMI_REQUIRE(a.ldw % 16 == 0, "attn_oproj: ldw must be a multiple of 16 elements (16-B row slices)");
     LLMI_REQUIRE(a.max_seq > 0 && (a.max_seq + CH - 1) / CH <= kMaxSplits, "attn_oproj: max_seq out of range");
     LLMI_REQUIRE(a.nact >= 0 && a.nact <= (a.max_seq + CH - 1) / CH, "attn_oproj: nact out of range");
     switch (a.w_dtype) {

@@ -114,6 +114,66 @@ int llmi_debug_stream_k(int mode, int launches) {
     return LLMI_OK;
 }
 
+namespace {
+GemvArgs debug_gemv_args(const llmi_debug_gemv_args& d) {
+    GemvArgs a;
+    a.w = d.w; a.scales = reinterpret_cast<const __half*>(d.scales); a.w_dtype = d.w_dtype;
+    a.n_rows = d.n_rows; a.k = d.k; a.ldw = d.ldw;
+    a.x = d.x; a.x_fixed = d.x_fixed; a.x_out = d.x_out;
+    a.gamma = d.gamma; a.g_dtype = d.g_dtype; a.eps = d.eps != 0.f ? d.eps : 1e-5f;
+    a.epi = d.epi; a.y = d.y; a.resid = d.resid; a.resid_scale = d.resid_scale; a.pair_off = d.pair_off;
+    a.partials = d.partials; a.idx_base = d.idx_base; a.grid = d.grid;
+    a.ksplit = d.ksplit != 0 ? d.ksplit : 1; a.yacc = d.yacc;
+    a.yacc_single = d.yacc_single; a.yacc_base = d.yacc_base; a.yacc_copy = d.yacc_copy;
+    a.seed_src = d.seed_src; a.seed_dst = d.seed_dst; a.seed_n = d.seed_n; a.seed_keep = d.seed_keep;
+    a.kpar = d.kpar;
+    return a;
+}
+}  // namespace
+
+int llmi_debug_gemv(const llmi_debug_gemv_args* args, llmi_stream_t stream) {
+    LLMI_REQUIRE(args != nullptr, "debug_gemv: null arguments");
+    LLMI_REQUIRE(args->epi >= EPI_STORE && args->epi <= EPI_ATOMIC, "debug_gemv: epi must be 0..4");
+    LLMI_REQUIRE(args->grid >= 0 && args->seed_n >= 0 && (!args->seed_dst || !args->seed_keep || args->seed_src),
+                 "debug_gemv: bad grid or seed arguments");
+    return gemv_launch(debug_gemv_args(*args), STREAM(stream));
+}
+
+int llmi_debug_gemv_plan(const llmi_debug_gemv_args* args, int* grid, int* unroll, int* xpt) {
+    LLMI_REQUIRE(args != nullptr, "debug_gemv_plan: null arguments");
+    LLMI_REQUIRE(args->epi >= EPI_STORE && args->epi <= EPI_ATOMIC, "debug_gemv_plan: epi must be 0..4");
+    return gemv_plan(debug_gemv_args(*args), grid, unroll, xpt);
+}
+
+int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t stream) {
+    LLMI_REQUIRE(args != nullptr, "debug_attn_oproj: null arguments");
+    const llmi_debug_attn_oproj_args& d = *args;
+    LLMI_REQUIRE(d.pos_dev && d.xacc && d.err && d.n_rows > 0, "debug_attn_oproj: pos_dev, xacc, err and n_rows needed");
+    LLMI_REQUIRE(d.resid || d.resid_fixed, "debug_attn_oproj: the xacc seed needs resid or resid_fixed");
+    AttnArgs at;
+    at.qkv = d.qkv; at.k_cache = d.k_cache; at.v_cache = d.v_cache; at.cache_dtype = d.cache_dtype;
+    at.max_seq = d.max_seq; at.pos_dev = d.pos_dev; at.nact = d.nact;
+    at.heads = d.heads; at.kv_heads = d.kv_heads; at.head_dim = d.head_dim ? d.head_dim : 128;
+    at.rope = d.rope; at.rope_base = d.rope_base != 0.f ? d.rope_base : 10000.f;
+    at.workspace = d.workspace;
+    at.direct_out = 0;  // partials only: the o_proj launch merges them
+    at.xacc = d.xacc; at.resid = d.resid; at.resid_fixed = d.resid_fixed; at.resid_scale = d.resid_scale;
+    at.hidden = d.n_rows;
+    at.err = d.err;
+    OprojArgs o;
+    o.w = d.w; o.scales = reinterpret_cast<const __half*>(d.scales); o.w_dtype = d.w_dtype;
+    o.head_major = d.head_major; o.n_rows = d.n_rows; o.ldw = d.ldw;
+    o.heads = d.heads; o.head_dim = at.head_dim; o.max_seq = d.max_seq;
+    o.pos_dev = d.pos_dev; o.nact = d.nact;
+    o.workspace = d.workspace; o.xacc = d.xacc; o.err = d.err;
+    // both argument checks before either launch: a rejected o_proj leaves xacc unseeded too
+    LLMI_REQUIRE(o.w && o.ldw >= o.heads * 128 && o.ldw % 16 == 0 && (o.w_dtype != LLMI_I8 || o.scales) &&
+                     (o.w_dtype == LLMI_F16 || o.w_dtype == LLMI_F32 || o.w_dtype == LLMI_I8),
+                 "debug_attn_oproj: bad W_o arguments");
+    LLMI_TRY(attn_decode_launch(at, STREAM(stream)));
+    return attn_oproj_launch(o, STREAM(stream));
+}
+
 int llmi_debug_prefill_stamps(void* stamps) {
     prefill_stamps_debug(static_cast<unsigned long long*>(stamps));
     return LLMI_OK;

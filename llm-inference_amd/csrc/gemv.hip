@@ -40,7 +40,7 @@ int epl_of(int dt) { return dt == LLMI_F16 ? 8 : dt == LLMI_F32 ? 4 : dt == LLMI
 
 int gemv_grid(const GemvArgs& a) {
     if (a.grid > 0) return a.grid;
-    const int groups = (a.epi == EPI_SILU_MUL) ? a.pair_off : (a.n_rows + kRows - 1) / kRows;
+    const int groups = gemv_groups(a);
     if (a.kpar > 1) return (groups + kWavesPerBlock / a.kpar - 1) / (kWavesPerBlock / a.kpar);  // a group per wave
     int blocks = (groups + kWavesPerBlock - 1) / kWavesPerBlock;
     // cap (default ~4 workgroups per CU on 256 CUs); waves then loop over several row groups
@@ -49,7 +49,9 @@ int gemv_grid(const GemvArgs& a) {
     return (blocks < cap ? blocks : cap) * S;
 }
 
-int gemv_launch(const GemvArgs& a, hipStream_t s) {
+namespace {
+// the argument contract of gemv_launch (and of gemv_plan, which launches nothing)
+int gemv_check(const GemvArgs& a) {
     const int epl = epl_of(a.w_dtype);
     LLMI_REQUIRE(epl > 0, "gemv: weight dtype must be f16, f32 or i8");
     LLMI_REQUIRE(a.k > 0 && a.k % epl == 0, "gemv: k must be a positive multiple of 16 bytes of weights");
@@ -65,10 +67,28 @@ int gemv_launch(const GemvArgs& a, hipStream_t s) {
                                          a.k % (a.ksplit * epl) == 0),
                  "gemv: EPI_ATOMIC needs yacc, an fp32 x and k divisible into ksplit 16-B slices");
     LLMI_REQUIRE(a.epi == EPI_ATOMIC || a.ksplit == 1, "gemv: ksplit only with EPI_ATOMIC");
+    // single producer: a second K slice would overwrite the first one's row instead of adding to it
+    LLMI_REQUIRE(!a.yacc_single || (a.epi == EPI_ATOMIC && a.ksplit == 1),
+                 "gemv: yacc_single needs EPI_ATOMIC with ksplit 1 (one producer per row)");
     LLMI_REQUIRE(a.kpar <= 1 || ((a.kpar == 2 || a.kpar == 4) && (a.epi == EPI_STORE || a.epi == EPI_SILU_MUL) &&
                                  a.grid == 0 && (a.k / epl) % a.kpar == 0),
                  "gemv: kpar 2 / 4 needs a store or silu epilogue, an automatic grid and k / kpar whole 16-B chunks");
-    LLMI_REQUIRE(a.ldw == 0 || a.ldw >= a.k, "gemv: ldw < k");
+    LLMI_REQUIRE(a.ldw == 0 || (a.ldw >= a.k && a.ldw % epl == 0), "gemv: ldw < k or rows not 16-B aligned");
+    return LLMI_OK;
+}
+}  // namespace
+
+int gemv_plan(const GemvArgs& a, int* grid, int* unroll, int* xpt) {
+    LLMI_TRY(gemv_check(a));
+    const int kl = (a.epi == EPI_ATOMIC) ? a.k / a.ksplit : a.k;  // x extent one workgroup stages (launch_u)
+    if (grid) *grid = gemv_grid(a);
+    if (unroll) *unroll = gemv_pick_unroll(epl_of(a.w_dtype), a.epi, a, gemv_groups(a));
+    if (xpt) *xpt = gemv_xpt(kl / 4);
+    return LLMI_OK;
+}
+
+int gemv_launch(const GemvArgs& a, hipStream_t s) {
+    LLMI_TRY(gemv_check(a));
     const int grid = gemv_grid(a);
     switch (a.w_dtype) {
         case LLMI_F16: return launch_epi<__half>(a, grid, s);

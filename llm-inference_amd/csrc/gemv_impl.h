@@ -85,6 +85,46 @@ __host__ __device__ inline size_t gemv_lds_bytes(int k) {
     return (size_t)k * 4 + 16 * 4 + kWavesPerBlock * 8 + kWavesPerBlock * 2 * 4;  // + kpar partials [4][2]
 }
 
+// Row groups of a launch: a wave owns one group at a time (a gate/up pair, else kRows rows)
+inline int gemv_groups(const GemvArgs& a) {
+    return (a.epi == EPI_SILU_MUL) ? a.pair_off : (a.n_rows + kRows - 1) / kRows;
+}
+
+// The x-staging width (XPT below) instantiated for an x of k4 float4s: the narrowest of the
+// preset widths that holds it, else the generic strided staging
+inline int gemv_xpt(int k4) {
+    if (k4 <= 4 * kThreads) return 4;
+    if (k4 <= 5 * kThreads) return 5;    // 13B hidden
+    if (k4 <= 11 * kThreads) return 11;  // 7B inter
+    if (k4 <= 14 * kThreads) return 14;  // 13B inter
+    return 0;
+}
+
+// Loads in flight per wave: measured on MI355X (tools/tune_gemv.sh, profiles/):
+// with many row groups per CU (q/k/v, gate_up) 2 rows x 4 loads per wave win
+// (more waves resident); with few groups (o, down: 2048 pairs; lm_head argmax)
+// 2 rows x 8 loads per wave win.
+// Unroll (16-B loads per row in flight per lane; a batch covers 64 * U chunks of a
+// row). Preference measured on MI355X (tools/tune_gemv.sh, profiles/): with many
+// row groups per CU (q/k/v, gate_up) U = 4 (more waves resident), otherwise U = 8.
+// A U that pads the row's chunk count to fewer batch slots wins over the
+// preference: masked slots cost load issue and VALU (13B rows: 320 int8 / 640
+// fp16 chunks waste 37.5 % / 25 % of their slots at U = 8, none at U = 5).
+// epl: weight elements per 16-B chunk; epi: the launch's epilogue.
+inline int gemv_pick_unroll(int epl, int epi, const GemvArgs& a, int groups) {
+    const int kl = (epi == EPI_ATOMIC) ? a.k / a.ksplit : a.k;
+    const int nc = kl / epl / (a.kpar > 1 ? a.kpar : 1);  // chunks one wave streams
+    auto slots = [&](int u) { const int b = kWave * u; return (nc + b - 1) / b * b; };
+    // kpar: only U = 4 is instantiated for the K-parted kernel (launch_u), so it is taken
+    // whatever the slot count (13B fp16 at kpar 2: 320 chunks a part would pick U = 5 and
+    // fail the launch)
+    if (a.kpar > 1) return 4;
+    int best = (epi != EPI_ARGMAX && groups >= 4096 && groups <= 12288 && kUnrollMax >= 4) ? 4 : kUnrollMax;
+    for (int u : {4, 5, 8})
+        if (u <= kUnrollMax && slots(u) < slots(best)) best = u;
+    return best;
+}
+
 // XPT: float4s of x each thread holds in registers during staging (k <= XPT*4*256);
 // 0 = generic strided staging (standalone only).
 // bid / nblk: this workgroup's index in the GEMV grid and the grid size.

@@ -83,49 +83,33 @@ int launch_u(const GemvArgs& a, int grid, hipStream_t s) {
     const int kl = (EPI == EPI_ATOMIC) ? a.k / a.ksplit : a.k;  // x extent one workgroup stages
     const size_t lds = gemv_lds_bytes(kl);
     const int k4 = kl / 4;
+    const int xpt = gemv_xpt(k4);  // the staging width (gemv_impl.h)
     if constexpr ((EPI == EPI_STORE || EPI == EPI_SILU_MUL) && NORM && XF && U == 4) {
         // kpar (a TP rank's q/k/v and gate_up): the engine's normed fixed-point projections,
         // hidden <= 5120
         if (a.kpar > 1) {
             LLMI_REQUIRE(k4 <= 5 * kThreads, "gemv: kpar needs k <= 5120");
             if (a.kpar == 2)
-                return k4 <= 4 * kThreads ? launch_k<WT, ROWS, EPI, NORM, GT, 4, U, XF, 2>(a, grid, lds, s)
-                                          : launch_k<WT, ROWS, EPI, NORM, GT, 5, U, XF, 2>(a, grid, lds, s);
-            return k4 <= 4 * kThreads ? launch_k<WT, ROWS, EPI, NORM, GT, 4, U, XF, 4>(a, grid, lds, s)
-                                      : launch_k<WT, ROWS, EPI, NORM, GT, 5, U, XF, 4>(a, grid, lds, s);
+                return xpt == 4 ? launch_k<WT, ROWS, EPI, NORM, GT, 4, U, XF, 2>(a, grid, lds, s)
+                                : launch_k<WT, ROWS, EPI, NORM, GT, 5, U, XF, 2>(a, grid, lds, s);
+            return xpt == 4 ? launch_k<WT, ROWS, EPI, NORM, GT, 4, U, XF, 4>(a, grid, lds, s)
+                            : launch_k<WT, ROWS, EPI, NORM, GT, 5, U, XF, 4>(a, grid, lds, s);
         }
     }
     LLMI_REQUIRE(a.kpar <= 1, "gemv: kpar only for the engine's normed fixed-point q/k/v and gate_up");
-    if (k4 <= 4 * kThreads) return launch_k<WT, ROWS, EPI, NORM, GT, 4, U, XF>(a, grid, lds, s);
-    if (k4 <= 5 * kThreads) return launch_k<WT, ROWS, EPI, NORM, GT, 5, U, XF>(a, grid, lds, s);    // 13B hidden
-    if (k4 <= 11 * kThreads) return launch_k<WT, ROWS, EPI, NORM, GT, 11, U, XF>(a, grid, lds, s);  // 7B inter
-    if (k4 <= 14 * kThreads) return launch_k<WT, ROWS, EPI, NORM, GT, 14, U, XF>(a, grid, lds, s);  // 13B inter
+    switch (xpt) {
+        case 4: return launch_k<WT, ROWS, EPI, NORM, GT, 4, U, XF>(a, grid, lds, s);
+        case 5: return launch_k<WT, ROWS, EPI, NORM, GT, 5, U, XF>(a, grid, lds, s);
+        case 11: return launch_k<WT, ROWS, EPI, NORM, GT, 11, U, XF>(a, grid, lds, s);
+        case 14: return launch_k<WT, ROWS, EPI, NORM, GT, 14, U, XF>(a, grid, lds, s);
+    }
     return launch_k<WT, ROWS, EPI, NORM, GT, 0, U, XF>(a, grid, lds, s);
 }
 
-// Loads in flight per wave: measured on MI355X (tools/tune_gemv.sh, profiles/):
-// with many row groups per CU (q/k/v, gate_up) 2 rows x 4 loads per wave win
-// (more waves resident); with few groups (o, down: 2048 pairs; lm_head argmax)
-// 2 rows x 8 loads per wave win.
-// Unroll (16-B loads per row in flight per lane; a batch covers 64 * U chunks of a
-// row). Preference measured on MI355X (tools/tune_gemv.sh, profiles/): with many
-// row groups per CU (q/k/v, gate_up) U = 4 (more waves resident), otherwise U = 8.
-// A U that pads the row's chunk count to fewer batch slots wins over the
-// preference: masked slots cost load issue and VALU (13B rows: 320 int8 / 640
-// fp16 chunks waste 37.5 % / 25 % of their slots at U = 8, none at U = 5).
+// the unroll gemv_pick_unroll (gemv_impl.h) chooses for this weight type and epilogue
 template <typename WT, int EPI>
 int pick_unroll(const GemvArgs& a, int groups) {
-    const int kl = (EPI == EPI_ATOMIC) ? a.k / a.ksplit : a.k;
-    const int nc = kl / WT_<WT>::EPL / (a.kpar > 1 ? a.kpar : 1);  // chunks one wave streams
-    auto slots = [&](int u) { const int b = kWave * u; return (nc + b - 1) / b * b; };
-    // kpar: only U = 4 is instantiated for the K-parted kernel (launch_u), so it is taken
-    // whatever the slot count (13B fp16 at kpar 2: 320 chunks a part would pick U = 5 and
-    // fail the launch)
-    if (a.kpar > 1) return 4;
-    int best = (EPI != EPI_ARGMAX && groups >= 4096 && groups <= 12288 && kUnrollMax >= 4) ? 4 : kUnrollMax;
-    for (int u : {4, 5, 8})
-        if (u <= kUnrollMax && slots(u) < slots(best)) best = u;
-    return best;
+    return gemv_pick_unroll(WT_<WT>::EPL, EPI, a, groups);
 }
 
 template <typename WT, int ROWS, int EPI, bool NORM, typename GT, bool XF>
@@ -137,8 +121,8 @@ int launch_x(const GemvArgs& a, int grid, int u, hipStream_t s) {
 
 template <typename WT, int ROWS, int EPI, bool NORM, typename GT>
 int launch_t(const GemvArgs& a, int grid, hipStream_t s) {
-    const int groups = (EPI == EPI_SILU_MUL) ? a.pair_off : (a.n_rows + ROWS - 1) / ROWS;
-    const int u = pick_unroll<WT, EPI>(a, groups);
+    static_assert(ROWS == (EPI == EPI_SILU_MUL ? 2 : kRows), "gemv_groups counts groups of these rows");
+    const int u = pick_unroll<WT, EPI>(a, gemv_groups(a));
     if (a.x_fixed) {
         // the engine's residual stream is int64 fixed point: the normed projections read it
         if constexpr (NORM && EPI != EPI_ADD && EPI != EPI_ATOMIC) {

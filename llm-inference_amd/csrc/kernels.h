@@ -97,6 +97,9 @@ struct GemvArgs {
 
 int gemv_launch(const GemvArgs& a, hipStream_t s);
 int gemv_grid(const GemvArgs& a);  // blocks gemv_launch will use
+// what gemv_launch would instantiate for a, nothing launched: gemv_grid, the unroll and the
+// x-staging width XPT (gemv_impl.h), from the functions the launcher itself calls
+int gemv_plan(const GemvArgs& a, int* grid, int* unroll, int* xpt);
 
 // ------------------------------------------------------ prefill GEMM (MFMA)
 // Y[m, n] (op)= sum_k A[m, k] W[n, k] for M prompt rows; see gemm.hip.

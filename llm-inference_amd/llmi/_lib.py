@@ -33,6 +33,33 @@ class Config(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebugGemvArgs(C.Structure):
+    """llmi_debug_gemv_args (include/llmi.h), field for field; pointers are device addresses."""
+    _fields_ = [("w", C.c_void_p), ("scales", C.c_void_p),
+                ("w_dtype", C.c_int), ("n_rows", C.c_int), ("k", C.c_int), ("ldw", C.c_int),
+                ("x", C.c_void_p), ("x_fixed", C.c_void_p), ("x_out", C.c_void_p),
+                ("gamma", C.c_void_p), ("g_dtype", C.c_int), ("eps", C.c_float),
+                ("epi", C.c_int), ("y", C.c_void_p), ("resid", C.c_void_p),
+                ("resid_scale", C.c_float), ("pair_off", C.c_int),
+                ("partials", C.c_void_p), ("idx_base", C.c_uint32), ("grid", C.c_int),
+                ("ksplit", C.c_int), ("yacc", C.c_void_p), ("yacc_single", C.c_int),
+                ("yacc_base", C.c_void_p), ("yacc_copy", C.c_void_p),
+                ("seed_src", C.c_void_p), ("seed_dst", C.c_void_p),
+                ("seed_n", C.c_int), ("seed_keep", C.c_int), ("kpar", C.c_int)]
+
+
+class DebugAttnOprojArgs(C.Structure):
+    """llmi_debug_attn_oproj_args (include/llmi.h), field for field."""
+    _fields_ = [("qkv", C.c_void_p), ("k_cache", C.c_void_p), ("v_cache", C.c_void_p),
+                ("cache_dtype", C.c_int), ("max_seq", C.c_int), ("pos_dev", C.c_void_p),
+                ("nact", C.c_int), ("heads", C.c_int), ("kv_heads", C.c_int), ("head_dim", C.c_int),
+                ("rope", C.c_int), ("rope_base", C.c_float), ("workspace", C.c_void_p),
+                ("xacc", C.c_void_p), ("resid", C.c_void_p), ("resid_fixed", C.c_void_p),
+                ("resid_scale", C.c_float), ("w", C.c_void_p), ("scales", C.c_void_p),
+                ("w_dtype", C.c_int), ("head_major", C.c_int), ("n_rows", C.c_int), ("ldw", C.c_int),
+                ("err", C.c_void_p)]
+
+
 _P, _I, _U64, _U32, _F, _SZ = C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_size_t
 _SIGS = {
     "llmi_last_error": (C.c_char_p, []),
@@ -68,6 +95,9 @@ _SIGS = {
     "llmi_ffn_residual": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _F, _P]),
     "llmi_stream_errors": (_I, [_P, _P]),
     "llmi_debug_stream_k": (_I, [_I, _I]),
+    "llmi_debug_gemv": (_I, [C.POINTER(DebugGemvArgs), _P]),
+    "llmi_debug_gemv_plan": (_I, [C.POINTER(DebugGemvArgs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "llmi_debug_attn_oproj": (_I, [C.POINTER(DebugAttnOprojArgs), _P]),
     "llmi_debug_prefill_stamps": (_I, [_P]),
     "llmi_hbm_read_bench": (_I, [_SZ, _I, _P, _P, _P]),
     "llmi_batched_matmul": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),

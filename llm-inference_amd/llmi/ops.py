@@ -352,6 +352,48 @@ def debug_stream_k(mode: int, launches: int = 1) -> None:
     call("llmi_debug_stream_k", int(mode), int(launches))
 
 
+def _debug_args(cls, fields):
+    a = cls()
+    names = {n for n, _ in cls._fields_}
+    for key, v in fields.items():
+        if key not in names:
+            raise TypeError(f"{cls.__name__} has no field {key!r}")
+        if isinstance(v, torch.Tensor):
+            _dev(v)
+            v = v.data_ptr()
+        if v is not None:
+            setattr(a, key, v)
+    return a
+
+
+def debug_gemv(**fields) -> None:
+    """llmi_debug_gemv (test hook): one launch of the decode GEMV with llmi_debug_gemv_args
+    filled from the keywords (tensors become their device addresses; the rest stays zero,
+    resid_scale defaults to 1). The caller owns every buffer."""
+    fields.setdefault("resid_scale", 1.0)
+    a = _debug_args(_lib.DebugGemvArgs, fields)
+    call("llmi_debug_gemv", ctypes.byref(a), _stream())
+
+
+def debug_gemv_plan(**fields):
+    """llmi_debug_gemv_plan (test hook): (grid, unroll, xpt) llmi_debug_gemv would use for the
+    same keywords; launches nothing."""
+    fields.setdefault("resid_scale", 1.0)
+    a = _debug_args(_lib.DebugGemvArgs, fields)
+    g, u, x = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    call("llmi_debug_gemv_plan", ctypes.byref(a), ctypes.byref(g), ctypes.byref(u), ctypes.byref(x))
+    return g.value, u.value, x.value
+
+
+def debug_attn_oproj(**fields) -> None:
+    """llmi_debug_attn_oproj (test hook): the engine's split-KV attention launch and its o_proj
+    launch on the current stream, llmi_debug_attn_oproj_args filled from the keywords
+    (resid_scale defaults to 1); the result is left in xacc."""
+    fields.setdefault("resid_scale", 1.0)
+    a = _debug_args(_lib.DebugAttnOprojArgs, fields)
+    call("llmi_debug_attn_oproj", ctypes.byref(a), _stream())
+
+
 def stream_errors() -> int:
     """llmi_stream_errors: read and clear the device error bits recorded on the current stream
     by the layer-API GEMM calls (16: a stream-K partial never arrived; synchronises)."""

@@ -78,3 +78,32 @@ def test_errors_are_codes_with_messages():
     h = C.c_void_p()
     rc = L.llmi_engine_create(C.byref(cfg), 0, None, C.byref(h))
     assert rc == -1 and b"divide by tp_world" in L.llmi_last_error()
+
+
+def test_debug_gemv_plan_reports_the_launchers_choices():
+    """llmi_debug_gemv_plan launches nothing, so its ladder is checked without a GPU: the
+    x-staging width at each threshold (k / 4 float4s against 4, 5, 11, 14 x 256), the unroll
+    that pads the row's chunk count least, the grid of each form, and the launcher's argument
+    checks (the plan runs the same ones)."""
+    F = 0x1000  # never dereferenced
+
+    def plan(**kw):
+        a = _lib.DebugGemvArgs()
+        for key, v in dict(dict(w=F, scales=F, x=F, y=F, w_dtype=_lib.F16, n_rows=37, k=4096), **kw).items():
+            setattr(a, key, v)
+        g, u, x = C.c_int(), C.c_int(), C.c_int()
+        call("llmi_debug_gemv_plan", C.byref(a), C.byref(g), C.byref(u), C.byref(x))
+        return g.value, u.value, x.value
+
+    assert [plan(k=k)[2] for k in (4096, 4104, 5120, 5128, 11264, 11272, 14336, 14344)] == [4, 5, 5, 11, 11, 14, 14, 0]
+    assert [plan(k=k)[1] for k in (2048, 2560, 4096, 13824)] == [4, 5, 8, 4]         # 256, 320, 512, 1728 chunks
+    assert plan(k=5120, w_dtype=_lib.I8)[1:] == (5, 5) and plan(k=5120, w_dtype=_lib.F32)[1:] == (4, 5)
+    assert plan()[0] == 5 and plan(grid=3)[0] == 3
+    assert plan(n_rows=1536, x=0, x_fixed=F, gamma=F, kpar=2)[:2] == (384, 4)       # one group a wave pair
+    assert plan(n_rows=4096, epi=4, yacc=F, ksplit=8) == (1024, 4, 4)                # 128 blocks x 8 slices of 64 chunks
+    assert plan(n_rows=16384, epi=3, partials=F)[0] == 1024                          # the grid cap
+    assert plan(n_rows=2 * 11008, epi=2, pair_off=11008)[:2] == (1024, 4)            # many groups: unroll 4
+    for bad in (dict(epi=4, yacc=F, yacc_single=1, ksplit=2), dict(yacc_single=1), dict(ldw=4098), dict(ldw=4088),
+                dict(epi=5), dict(kpar=2, grid=2), dict(k=4100)):
+        with pytest.raises(_lib.LlmiError):
+            plan(**bad)
