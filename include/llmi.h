@@ -420,6 +420,17 @@ int llmi_synth_fill(void* out, int out_dtype, int kind, uint64_t seed, uint32_t 
 /* Host (CPU) twin of llmi_synth_fill, for checking the generator without a GPU. */
 int llmi_synth_fill_host(void* out, int out_dtype, int kind, uint64_t seed, uint32_t tid, int rows,
                          int cols, int row0, int col0, int ld);
+/* W8A16 quantiser (quant.hip; definition in DESIGN.md, int8 section): fp32 w [rows, ld]
+ * with row_len data columns -> int8 q [rows, cols] (dense) = the columns [col0, col0 + cols)
+ * and one fp16 scale per row, w ~= q * s. Per row: amax over all row_len columns (not only
+ * the written slice; [row_len, ld) is padding and never read), s = fp16_rne(amax / 127)
+ * (fp16 zero -> 2^-24, overflow -> 65504), q = clamp(rint(w / s), -127, 127) with correctly
+ * rounded fp32 divisions and round-half-even. A row holding a NaN or an infinity gets s = 0,
+ * q = 0 and adds 1 to *bad_rows (device counter the caller zeroes; may be NULL). All
+ * pointers are device pointers; ld, row_len, col0 and cols are multiples of 4 with
+ * col0 + cols <= row_len <= ld; w 16-byte aligned, q 4-byte. */
+int llmi_quantize_rows_i8(const float* w, size_t ld, int rows, int row_len, int col0, int cols, int8_t* q,
+                          void* scales /* fp16[rows] */, int32_t* bad_rows, llmi_stream_t stream);
 /* Device memory for host-side callers that include no HIP headers (the C++
  * mirror in include/llmi/): hipMalloc / hipFree / hipMemcpy / hipDeviceSynchronize.
  * kind: 0 host->device, 1 device->host, 2 device->device. */
@@ -494,10 +505,20 @@ int llmi_engine_load_synthetic(llmi_engine* e, uint64_t seed);
  * model.embed_tokens.weight, lm_head.weight, model.norm.weight and per layer l
  * model.layers.<l>.{input_layernorm, post_attention_layernorm, self_attn.qkv, self_attn.o_proj,
  * mlp.gate_up_proj, mlp.down_proj}.weight (unsharded shapes; this rank's slice is taken).
- * fp32 -> fp16 is round-to-nearest-even. int8 engines are refused (no reference format). */
+ * fp32 -> fp16 is round-to-nearest-even. int8 engines are refused here (the reference has
+ * no int8 format): they take the same files through llmi_engine_load_bin_quantized. */
 int llmi_engine_load_bin(llmi_engine* e, const char* weight_path);
 /* One tensor of the same set from a host fp32 buffer (name without ".bin"; count checked). */
 int llmi_engine_load_tensor(llmi_engine* e, const char* name, const float* host, size_t count);
+/* The same loaders for an LLMI_I8 engine (any other: LLMI_EINVAL, "quantize needs an int8
+ * engine"): same names, counts and files. The four linear tensors are uploaded as fp32 (whole
+ * rows, at most 256 MiB staged at a time, freed on return) and quantised to W8A16 by
+ * llmi_quantize_rows_i8 into the engine's int8 weights and fp16 row scales; the column-sharded
+ * o_proj and down take each scale from the whole unsharded row, so every TP rank holds the
+ * same scales. Norms, lm_head and the embedding are loaded as by llmi_engine_load_bin (fp16).
+ * A linear tensor holding a NaN or an infinity fails with a message naming it. */
+int llmi_engine_load_bin_quantized(llmi_engine* e, const char* weight_path);
+int llmi_engine_load_tensor_quantized(llmi_engine* e, const char* name, const float* host, size_t count);
 /* Llama<T>::Sampling (llama.cpp:245-262: launchTopKforBeamSearch + launchSampling) inside the
  * decode step: k in [1, 16] samples each generated token from the top k logits with
  * sampling.cu's rule, u = curand_uniform(curand_init(step, 0, 0)) (cuRAND XORWOW restated)
@@ -633,6 +654,8 @@ int llmi_group_create(const llmi_config* cfg, int world, int device, llmi_group*
 int llmi_group_destroy(llmi_group* g);
 int llmi_group_load_synthetic(llmi_group* g, uint64_t seed);
 int llmi_group_load_bin(llmi_group* g, const char* weight_path);
+/* llmi_engine_load_bin_quantized on every rank (int8 groups) */
+int llmi_group_load_bin_quantized(llmi_group* g, const char* weight_path);
 int llmi_group_set_prompt(llmi_group* g, const int32_t* ids, int n);
 int llmi_group_decode(llmi_group* g, int n_steps, int use_graph);
 /* tokens as seen by one rank (every rank must agree) */

@@ -43,6 +43,10 @@ public:
     void loadWeightsFromDummy(uint64_t seed = 0) { LLMI_CALL(llmi_engine_load_synthetic(eng, seed)); }
     // Llama<T>::loadWeights(weight_path) (llama_weights.cc:41-53): weight_path + "<name>.bin", raw fp32
     void loadWeights(const std::string& weight_path) { LLMI_CALL(llmi_engine_load_bin(eng, weight_path.c_str())); }
+    // the same files into an LLMI_I8 model: the linear weights are quantised to W8A16 on the device
+    void loadWeightsQuantized(const std::string& weight_path) {
+        LLMI_CALL(llmi_engine_load_bin_quantized(eng, weight_path.c_str()));
+    }
     // Llama<T>::Sampling's top-k (llama.cpp:245-262) in the decode step; k = 0 (default) is greedy
     void setSampling(int k, uint64_t seed = 0) { LLMI_CALL(llmi_engine_set_sampling(eng, k, seed)); }
 
@@ -90,9 +94,12 @@ private:
 // token-id variants of model_utils.h:63-82 (preset name instead of the template type)
 inline std::unique_ptr<LlamaModel> CreateRealLLMModel(const std::string& weight_path,
                                                       const std::string& preset = "llama2-7b",
-                                                      int weight_dtype = LLMI_F16) {
+                                                      int weight_dtype = LLMI_F16, bool quantize = false) {
     auto m = std::make_unique<LlamaModel>(preset, weight_dtype);
-    m->loadWeights(weight_path);
+    if (quantize)  // weight_dtype LLMI_I8: W8A16 from the fp32 files
+        m->loadWeightsQuantized(weight_path);
+    else
+        m->loadWeights(weight_path);
     return m;
 }
 

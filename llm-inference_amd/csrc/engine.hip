@@ -213,6 +213,11 @@ struct Engine {
     unsigned* rl_cnt = nullptr;
     char* wdt_blob = nullptr;
     bool wdt_valid = false;
+    // quantised loads (load_tensor with quantize): fp32 staging rows for quant.hip, the bad-row
+    // counter in its first 256 bytes; lives for one load (qstage_hold: a load_bin spans tensors)
+    char* qstage = nullptr;
+    size_t qstage_bytes = 0;
+    bool qstage_hold = false;
     long long* acc_a(int l) const { static const int s[3] = {0, 1, 3}; return rl_acc + (size_t)s[l % 3] * c.hidden; }
     long long* acc_b(int l) const { return rl_acc + (size_t)(l % 2 ? 4 : 2) * c.hidden; }
     void* wdt_of(int l) const { return wdt_blob + (size_t)l * il * c.hidden * 2; }
@@ -255,6 +260,7 @@ struct Engine {
         if (rl_acc) (void)hipFree(rl_acc);
         if (rl_cnt) (void)hipFree(rl_cnt);
         if (wdt_blob) (void)hipFree(wdt_blob);
+        if (qstage) (void)hipFree(qstage);
         if (stream && own_stream) (void)hipStreamDestroy(stream);
     }
 
@@ -504,9 +510,61 @@ struct Engine {
         return LLMI_OK;
     }
 
+    // W8A16 on load: rows [row0, row0 + rows) of the host fp32 tensor src [*, src_ld] go to the
+    // device staging buffer (whole rows, at most kQStageBytes at a time) and through the
+    // quantiser: q [rows, cols] = columns [col0, col0 + cols), the scale from the whole row.
+    static constexpr size_t kQStageBytes = (size_t)256 << 20;
+    static constexpr size_t kQStageHead = 256;  // the bad-row counter, then 16-byte aligned rows
+    void quant_release() {
+        if (qstage) (void)hipFree(qstage);
+        qstage = nullptr;
+        qstage_bytes = 0;
+    }
+    int quant_put(const std::string& nm, const float* src, size_t src_ld, size_t row0, int rows, int col0, int cols,
+                  void* q_dst, size_t q_row_off, __half* s_dst) {
+        const size_t row_bytes = src_ld * 4;
+        LLMI_REQUIRE(row_bytes <= kQStageBytes, "load_tensor: a row exceeds the quantiser's staging buffer");
+        const int chunk = (int)std::min<size_t>((size_t)rows, kQStageBytes / row_bytes);
+        const size_t need = kQStageHead + (size_t)chunk * row_bytes;
+        if (need > qstage_bytes) {
+            LLMI_HIP(hipStreamSynchronize(stream));
+            quant_release();
+            LLMI_HIP(hipMalloc(&qstage, need));
+            qstage_bytes = need;
+        }
+        int32_t* bad = reinterpret_cast<int32_t*>(qstage);
+        float* rows_dev = reinterpret_cast<float*>(qstage + kQStageHead);
+        LLMI_HIP(hipMemsetAsync(bad, 0, 4, stream));
+        int8_t* q = static_cast<int8_t*>(q_dst) + q_row_off * (size_t)cols;
+        for (int r0 = 0; r0 < rows; r0 += chunk) {
+            const int n = std::min(chunk, rows - r0);
+            LLMI_HIP(hipMemcpyAsync(rows_dev, src + (row0 + r0) * src_ld, (size_t)n * row_bytes, hipMemcpyHostToDevice,
+                                    stream));
+            LLMI_TRY(quantize_rows_i8_launch(rows_dev, src_ld, n, (int)src_ld, col0, cols, q + (size_t)r0 * cols,
+                                             s_dst + q_row_off + r0, bad, stream));
+        }
+        int32_t nbad = 0;
+        LLMI_HIP(hipMemcpyAsync(&nbad, bad, 4, hipMemcpyDeviceToHost, stream));
+        LLMI_HIP(hipStreamSynchronize(stream));
+        if (nbad != 0) {
+            set_last_error("[llmi][ERROR] load_tensor: " + nm + " holds a NaN or an infinity in " +
+                           std::to_string(nbad) + " row(s); nothing usable was quantised from them");
+            return LLMI_EINVAL;
+        }
+        return LLMI_OK;
+    }
+
     // name: the reference's file stem without ".bin" (e.g. "model.layers.3.self_attn.qkv.weight")
-    int load_tensor(const char* name, const float* src, size_t count) {
+    // quantize (int8 engines only): the four linear tensors are quantised to W8A16 on the device
+    int load_tensor(const char* name, const float* src, size_t count, bool quantize = false) {
+        const int rc = load_tensor_impl(name, src, count, quantize);
+        if (!qstage_hold) quant_release();
+        return rc;
+    }
+
+    int load_tensor_impl(const char* name, const float* src, size_t count, bool quantize) {
         LLMI_REQUIRE(name && src, "load_tensor: null argument");
+        LLMI_REQUIRE(!quantize || wdt == LLMI_I8, "quantize needs an int8 engine");
         LLMI_TRY(weights_changed());
         const std::string nm(name);
         const size_t H = c.hidden, D = c.head_dim, QR = (size_t)c.heads * D, KR = (size_t)c.kv_heads * D;
@@ -520,8 +578,9 @@ struct Engine {
             return LLMI_OK;
         };
         auto lin_ok = [&]() -> int {
-            LLMI_REQUIRE(wdt != LLMI_I8, "load_tensor: int8 engines take synthetic weights only "
-                                         "(the reference's .bin format is fp32; W8A16 is build-defined)");
+            LLMI_REQUIRE(quantize || wdt != LLMI_I8,
+                         "load_tensor: int8 engines take fp32 weights only through the quantised loaders "
+                         "(llmi_engine_load_bin_quantized / llmi_engine_load_tensor_quantized), or synthetic ones");
             return LLMI_OK;
         };
         if (nm == "model.embed_tokens.weight") {
@@ -552,6 +611,11 @@ struct Engine {
         if (leaf == "self_attn.qkv.weight") {
             LLMI_TRY(lin_ok());
             LLMI_TRY(need((QR + 2 * KR) * H));
+            if (quantize) {
+                LLMI_TRY(quant_put(nm, src, H, r * ql, ql, 0, (int)H, L.qkv, 0, L.qkv_s));
+                LLMI_TRY(quant_put(nm, src, H, QR + r * kvrows, kvrows, 0, (int)H, L.qkv, ql, L.qkv_s));
+                return quant_put(nm, src, H, QR + KR + r * kvrows, kvrows, 0, (int)H, L.qkv, ql + kvrows, L.qkv_s);
+            }
             char* d = (char*)L.qkv;
             LLMI_TRY(put_host(d, wdt, src, H, ql, (int)H, r * ql, 0, stream));
             LLMI_TRY(put_host(d + (size_t)ql * H * ws, wdt, src, H, kvrows, (int)H, QR + r * kvrows, 0, stream));
@@ -561,17 +625,24 @@ struct Engine {
         if (leaf == "self_attn.o_proj.weight") {
             LLMI_TRY(lin_ok());
             LLMI_TRY(need(H * QR));
+            // column shard: every rank takes its scale from the whole unsharded row
+            if (quantize) return quant_put(nm, src, QR, 0, (int)H, (int)(r * ql), ql, L.o, 0, L.o_s);
             return put_host(L.o, wdt, src, QR, (int)H, ql, 0, r * ql, stream);
         }
         if (leaf == "mlp.gate_up_proj.weight") {
             LLMI_TRY(lin_ok());
             LLMI_TRY(need(2 * I * H));
+            if (quantize) {
+                LLMI_TRY(quant_put(nm, src, H, r * il, il, 0, (int)H, L.gu, 0, L.gu_s));
+                return quant_put(nm, src, H, I + r * il, il, 0, (int)H, L.gu, il, L.gu_s);
+            }
             LLMI_TRY(put_host(L.gu, wdt, src, H, il, (int)H, r * il, 0, stream));
             return put_host((char*)L.gu + (size_t)il * H * ws, wdt, src, H, il, (int)H, I + r * il, 0, stream);
         }
         if (leaf == "mlp.down_proj.weight") {
             LLMI_TRY(lin_ok());
             LLMI_TRY(need(H * I));
+            if (quantize) return quant_put(nm, src, I, 0, (int)H, (int)(r * il), il, L.down, 0, L.down_s);
             return put_host(L.down, wdt, src, I, (int)H, il, 0, r * il, stream);
         }
         set_last_error("[llmi][ERROR] load_tensor: unknown tensor " + nm);
@@ -579,7 +650,16 @@ struct Engine {
     }
 
     // Llama<T>::loadWeights(weight_path): weight_path + "<name>.bin" for every tensor.
-    int load_bin(const char* weight_path) {
+    int load_bin(const char* weight_path, bool quantize = false) {
+        LLMI_REQUIRE(!quantize || wdt == LLMI_I8, "quantize needs an int8 engine");
+        qstage_hold = true;  // one staging buffer for all the tensors, released on return
+        const int rc = load_bin_impl(weight_path, quantize);
+        qstage_hold = false;
+        quant_release();
+        return rc;
+    }
+
+    int load_bin_impl(const char* weight_path, bool quantize) {
         LLMI_REQUIRE(weight_path, "load_bin: null path");
         std::vector<std::string> names = {"model.norm.weight", "lm_head.weight", "model.embed_tokens.weight"};
         for (int l = 0; l < c.layers; ++l)
@@ -610,7 +690,7 @@ struct Engine {
                 set_last_error("[llmi][ERROR] load_bin: short read on " + path);
                 return LLMI_EINVAL;
             }
-            LLMI_TRY(load_tensor(nm.c_str(), buf.data(), buf.size()));
+            LLMI_TRY(load_tensor_impl(nm.c_str(), buf.data(), buf.size(), quantize));
         }
         return LLMI_OK;
     }
@@ -1593,6 +1673,18 @@ int llmi_engine_load_tensor(llmi_engine* e, const char* name, const float* host,
     return e->e.load_tensor(name, host, count);
 }
 
+int llmi_engine_load_tensor_quantized(llmi_engine* e, const char* name, const float* host, size_t count) {
+    LLMI_REQUIRE(e, "null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.load_tensor(name, host, count, true);
+}
+
+int llmi_engine_load_bin_quantized(llmi_engine* e, const char* weight_path) {
+    LLMI_REQUIRE(e, "null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.load_bin(weight_path, true);
+}
+
 int llmi_engine_set_sampling(llmi_engine* e, int k, uint64_t seed) {
     LLMI_REQUIRE(e, "null engine");
     LLMI_HIP(hipSetDevice(e->e.device));
@@ -1977,6 +2069,15 @@ int llmi_group_load_bin(llmi_group* g, const char* weight_path) {
     for (auto& e : g->g.r) {
         LLMI_HIP(hipSetDevice(e->device));
         LLMI_TRY(e->load_bin(weight_path));
+    }
+    return LLMI_OK;
+}
+
+int llmi_group_load_bin_quantized(llmi_group* g, const char* weight_path) {
+    LLMI_REQUIRE(g, "null group");
+    for (auto& e : g->g.r) {
+        LLMI_HIP(hipSetDevice(e->device));
+        LLMI_TRY(e->load_bin(weight_path, true));
     }
     return LLMI_OK;
 }

@@ -495,4 +495,10 @@ int synth_fill_launch(void* out, int out_dtype, int kind, uint64_t seed, uint32_
 int synth_fill_host(void* out, int out_dtype, int kind, uint64_t seed, uint32_t tid, int rows,
                     int cols, int row0, int col0, int ld);
 
+// ------------------------------------------------- W8A16 quantiser (quant.hip)
+// fp32 w [rows, ld] (row_len data columns) -> q [rows, cols] = the slice at col0 and one fp16
+// scale per row from the whole row's maximum; *bad_rows += rows holding a NaN / infinity
+int quantize_rows_i8_launch(const float* w, size_t ld, int rows, int row_len, int col0, int cols, int8_t* q,
+                            __half* scales, int32_t* bad_rows, hipStream_t s);
+
 }  // namespace llmi

@@ -105,6 +105,7 @@ _SIGS = {
     "llmi_synth_fill": (_I, [_P, _I, _I, _U64, _U32, _I, _I, _I, _I, _I, _P]),
     "llmi_synth_fill_host": (_I, [_P, _I, _I, _U64, _U32, _I, _I, _I, _I, _I]),
     "llmi_synth_prompt": (_I, [_U64, _I, _I, _P]),
+    "llmi_quantize_rows_i8": (_I, [_P, _SZ, _I, _I, _I, _I, _P, _P, _P, _P]),
     "llmi_device_alloc": (_I, [C.POINTER(_P), _SZ]),
     "llmi_device_memset": (_I, [_P, _I, _SZ]),
     "llmi_device_memset_async": (_I, [_P, _I, _SZ, _P]),
@@ -122,6 +123,8 @@ _SIGS = {
     "llmi_engine_load_bin": (_I, [_P, C.c_char_p]),
     "llmi_engine_set_sampling": (_I, [_P, _I, _U64]),
     "llmi_engine_load_tensor": (_I, [_P, C.c_char_p, _P, _SZ]),
+    "llmi_engine_load_bin_quantized": (_I, [_P, C.c_char_p]),
+    "llmi_engine_load_tensor_quantized": (_I, [_P, C.c_char_p, _P, _SZ]),
     "llmi_engine_set_prompt": (_I, [_P, _P, _I]),
     "llmi_engine_decode": (_I, [_P, _I, _I]),
     "llmi_engine_prefill": (_I, [_P, _I, _I]),
@@ -148,6 +151,7 @@ _SIGS = {
     "llmi_group_destroy": (_I, [_P]),
     "llmi_group_load_synthetic": (_I, [_P, _U64]),
     "llmi_group_load_bin": (_I, [_P, C.c_char_p]),
+    "llmi_group_load_bin_quantized": (_I, [_P, C.c_char_p]),
     "llmi_group_set_prompt": (_I, [_P, _P, _I]),
     "llmi_group_decode": (_I, [_P, _I, _I]),
     "llmi_group_tokens": (_I, [_P, _I, _P, _I, C.POINTER(_I)]),

@@ -69,14 +69,18 @@ class Engine:
         """Top-k stochastic sampling in the decode step (k = 0: greedy, the default)."""
         call("llmi_engine_set_sampling", self._h, int(k), int(seed))
 
-    def load_bin(self, weight_path: str):
+    def load_bin(self, weight_path: str, quantize: bool = False):
         """Llama<T>::loadWeights(weight_path): weight_path + "<name>.bin" raw fp32 files
-        (llmi/convert.py writes them); the path is used as a prefix, like the reference's."""
-        call("llmi_engine_load_bin", self._h, weight_path.encode())
+        (llmi/convert.py writes them); the path is used as a prefix, like the reference's.
+        quantize (int8 engines, which take the files no other way): the linear weights are
+        quantised to W8A16 on the device (llmi_engine_load_bin_quantized)."""
+        call("llmi_engine_load_bin_quantized" if quantize else "llmi_engine_load_bin", self._h,
+             weight_path.encode())
 
-    def load_tensor(self, name: str, values: np.ndarray):
+    def load_tensor(self, name: str, values: np.ndarray, quantize: bool = False):
         v = np.ascontiguousarray(values, dtype=np.float32)
-        call("llmi_engine_load_tensor", self._h, name.encode(), v.ctypes.data, v.size)
+        call("llmi_engine_load_tensor_quantized" if quantize else "llmi_engine_load_tensor", self._h,
+             name.encode(), v.ctypes.data, v.size)
 
     def set_prompt(self, ids):
         ids = np.ascontiguousarray(ids, dtype=np.int32)
@@ -221,8 +225,9 @@ class TPGroup:
     def load_synthetic(self, seed: int):
         call("llmi_group_load_synthetic", self._h, seed)
 
-    def load_bin(self, weight_path: str):
-        call("llmi_group_load_bin", self._h, weight_path.encode())
+    def load_bin(self, weight_path: str, quantize: bool = False):
+        call("llmi_group_load_bin_quantized" if quantize else "llmi_group_load_bin", self._h,
+             weight_path.encode())
 
     def tokens(self, rank: int = 0, n: Optional[int] = None) -> np.ndarray:
         n = self.cfg.max_seq + 1 if n is None else n

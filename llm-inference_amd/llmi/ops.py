@@ -176,6 +176,30 @@ def synth_fill(out: torch.Tensor, kind: int, seed: int, tid: int, rows: int, col
     return out
 
 
+def quantizeRowsInt8(w: torch.Tensor, col0: int = 0, cols: int = None, row_len: int = None):
+    """W8A16 quantiser (llmi_quantize_rows_i8): w fp32 [rows, ld], of which row_len columns
+    (default ld) are data -> (q int8 [rows, cols] = columns [col0, col0 + cols), scales fp16
+    [rows]) with w ~= q * s, the scale from the whole row. Raises LlmiError when a row holds a
+    NaN or an infinity (the error's bad_rows attribute is the kernel's count of such rows)."""
+    _dev(w)
+    if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous():
+        raise ValueError("quantizeRowsInt8: w must be a contiguous fp32 [rows, ld] tensor")
+    rows, ld = w.shape
+    row_len = ld if row_len is None else int(row_len)
+    cols = row_len - col0 if cols is None else int(cols)
+    q = torch.empty(rows, max(cols, 0), device=w.device, dtype=torch.int8)
+    scales = torch.empty(rows, device=w.device, dtype=torch.float16)
+    bad = torch.zeros(1, device=w.device, dtype=torch.int32)
+    call("llmi_quantize_rows_i8", w.data_ptr(), ld, rows, row_len, int(col0), cols, q.data_ptr(), scales.data_ptr(),
+         bad.data_ptr(), _stream())
+    n_bad = int(bad.item())
+    if n_bad:
+        err = _lib.LlmiError(f"quantizeRowsInt8: {n_bad} row(s) hold a NaN or an infinity")
+        err.bad_rows = n_bad
+        raise err
+    return q, scales
+
+
 # ---------------------------------------------- context-phase (prefill) operators
 def _i32(t):
     return t.to(torch.int32).contiguous()
