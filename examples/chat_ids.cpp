@@ -5,8 +5,11 @@
 //
 //   g++ -std=c++17 -I include examples/chat_ids.cpp -L llm-inference_amd/lib -lllmi
 //       -Wl,-rpath,$PWD/llm-inference_amd/lib -o chat_ids
-//   echo "1 306 4966 29871" | ./chat_ids [preset] [max_new]
+//   echo "1 306 4966 29871" | ./chat_ids [preset] [max_new] [top_p temperature repetition_penalty [seed]]
+// With the three trailing numbers the answer is sampled (LlamaModel::setSamplingParams);
+// without them it is greedy.
 #include <cstdio>
+#include <cstdlib>
 #include <iostream>
 #include <sstream>
 #include <string>
@@ -18,6 +21,10 @@ int main(int argc, char** argv) {
     const int max_new = argc > 2 ? std::atoi(argv[2]) : 256;  // output_token_limit (llama.h:29)
     try {
         auto llm_model = llm::CreateDummyLLMModel(preset);
+        if (argc >= 6)
+            llm_model->setSamplingParams(0, (float)std::atof(argv[3]), (float)std::atof(argv[4]),
+                                         (float)std::atof(argv[5]),
+                                         argc > 6 ? std::strtoull(argv[6], nullptr, 10) : 0);
         while (true) {
             std::printf("please input the question (token ids): ");
             std::fflush(stdout);

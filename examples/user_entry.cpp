@@ -7,8 +7,11 @@
 //
 //   g++ -std=c++17 -I include examples/user_entry.cpp -L llm-inference_amd/lib -lllmi
 //       -Wl,-rpath,$PWD/llm-inference_amd/lib -o user_entry
-//   ./user_entry tests/golden/llama2-7b-tokenizer.bin [weight_dir/]
+//   ./user_entry tests/golden/llama2-7b-tokenizer.bin [weight_dir/] [top_p temperature repetition_penalty [seed]]
+// With the three trailing numbers (Llama-2-chat publishes 0.9 0.6; e.g. 1.1 for the penalty)
+// Response samples (Llama<T>::setSamplingParams); without them it decodes greedily.
 #include <cstdio>
+#include <cstdlib>
 #include <iostream>
 #include <string>
 
@@ -16,13 +19,25 @@
 
 int main(int argc, char** argv) {
     if (argc < 2) {
-        std::fprintf(stderr, "usage: %s tokenizer.bin [weight_path_prefix]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s tokenizer.bin [weight_path_prefix] [top_p temperature repetition_penalty [seed]]\n",
+                     argv[0]);
         return 2;
     }
     const std::string tokenizer_path = argv[1];
+    auto numeric = [](const char* a) {
+        char* end = nullptr;
+        std::strtod(a, &end);
+        return end != a && *end == '\0';
+    };
+    const bool has_weights = argc > 2 && !numeric(argv[2]);
+    const int s0 = has_weights ? 3 : 2;  // first sampling argument
     try {
-        std::unique_ptr<BaseModel> llm_model = argc > 2 ? llm::CreateRealLLMModel<float>(argv[2], tokenizer_path)
-                                                        : llm::CreateDummyLLMModel<float>(tokenizer_path);
+        std::unique_ptr<BaseModel> llm_model = has_weights ? llm::CreateRealLLMModel<float>(argv[2], tokenizer_path)
+                                                           : llm::CreateDummyLLMModel<float>(tokenizer_path);
+        if (argc >= s0 + 3)
+            dynamic_cast<Llama<float>&>(*llm_model).setSamplingParams(
+                0, (float)std::atof(argv[s0]), (float)std::atof(argv[s0 + 1]), (float)std::atof(argv[s0 + 2]),
+                argc > s0 + 3 ? std::strtoull(argv[s0 + 3], nullptr, 10) : 0);
         const std::string name = llm_model->model_name;
         std::string history;
         for (int round = 0;; ++round) {

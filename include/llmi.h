@@ -296,6 +296,32 @@ int llmi_topk(const void* logits, int dtype, int rows, int vocab, int k, int32_t
 int llmi_sampling(const int32_t* topk_ids, void* topk_vals, int dtype, int rows, int k, int32_t* output_id,
                   int32_t* seqlen, uint8_t* is_finished, int step, int end_id, int vocab, llmi_stream_t stream);
 
+/* Temperature / top-k / top-p (nucleus) / repetition-penalty sampling over whole rows of
+ * logits [rows, vocab] (f32, not modified). No reference counterpart; the rule is specified
+ * in DESIGN.md ("Nucleus sampler") and restated in tests/nucleus_ref.py:
+ *   penalty (skipped at 1): for every distinct id of the row's history, z = z > 0 ? z / r : z * r;
+ *   temperature (skipped at 1): z = z / T (both divisions correctly rounded fp32);
+ *   order: value descending, ties to the lower id (llmi_argmax's order: top_k = 1 is llmi_argmax);
+ *   integer weights w = rint(expf(z - max) * 2^32); C = the first top_k of the order (0: all);
+ *   K = the shortest prefix of C whose weight is >= ceil(top_p * sum(C)) (top_p = 1: C);
+ *   the id returned is the first id of K, in ASCENDING ID order, whose running weight reaches
+ *   ceil(u * sum(K)), u = curand_uniform(curand_init(step, row, 0)) as in llmi_sampling.
+ * The id-order walk differs from llmi_sampling's value-order float walk: from the same u the
+ * two samplers do not choose the same token.
+ * Non-finite logits: -inf has weight 0; NaN (after penalty and temperature) counts as -inf;
+ * if the maximum is +inf, the +inf entries share the draw equally and every other id has weight
+ * 0 (a row of only -inf / NaN draws uniformly over all ids). The id is always in [0, vocab).
+ * history [rows, history_stride] device int32 with history_len[row] valid ids per row
+ * (history_len NULL: no history). out_kept (nullable) receives |K|. rows <= 65536,
+ * vocab <= 131072 (LLMI_EUNSUPPORTED above). LLMI_EINVAL: temperature <= 0, top_p outside
+ * (0, 1], repetition_penalty <= 0, top_k < 0, null pointers, history ids outside [0, vocab)
+ * (ids are read back and checked unless the stream is being captured; the kernel ignores
+ * such ids). Graph-capturable; allocates nothing but the XORWOW jump table (rows > 1, once). */
+int llmi_sample_nucleus(const float* logits, int rows, int vocab, const int32_t* history, int history_stride,
+                        const int32_t* history_len /* [rows], NULL: none */, float repetition_penalty,
+                        float temperature, int top_k, float top_p, uint64_t step, int32_t* out_id /* [rows] */,
+                        int32_t* out_kept /* [rows], nullable */, llmi_stream_t stream);
+
 /* The draw llmi_sampling makes, computed on the host (no device work): the first
  * curand_uniform of curand_init(seed, subsequence, 0) -- cuRAND's XORWOW as restated in
  * csrc/xorwow.h (subsequence < 65536). For checking the restatement against a CPU oracle. */
@@ -527,6 +553,18 @@ int llmi_engine_load_tensor_quantized(llmi_engine* e, const char* name, const fl
  * k = 0 restores greedy argmax (the default). Needs tp_world == 1. Applies to tokens chosen
  * by decode steps (a batched prefill's first token stays greedy). */
 int llmi_engine_set_sampling(llmi_engine* e, int k, uint64_t seed);
+/* llmi_sample_nucleus inside the token step (one launch after the lm_head, and after a
+ * prefill's last row): history = the sequence's ids up to the current position, read from
+ * the device decode state, step = seed + (the sampled token's position). top_k 0 = no limit,
+ * top_p 1 = no nucleus cut, temperature 1 and repetition_penalty 1 = off. Same checks as
+ * llmi_sample_nucleus; needs tp_world == 1 and is not available on a group rank. Replaces
+ * llmi_engine_set_sampling's sampler, and that call (any k, 0 included) replaces this one. */
+typedef struct llmi_sampling_params {
+    int top_k;
+    float top_p, temperature, repetition_penalty;
+    uint64_t seed;
+} llmi_sampling_params;
+int llmi_engine_set_sampling_params(llmi_engine* e, const llmi_sampling_params* p);
 /* Reset the sequence and stage a prompt (device copy). */
 int llmi_engine_set_prompt(llmi_engine* e, const int32_t* ids, int n);
 /* Run n forward steps (one token each). use_graph: replay the captured hipGraph. */

@@ -49,6 +49,13 @@ public:
     }
     // Llama<T>::Sampling's top-k (llama.cpp:245-262) in the decode step; k = 0 (default) is greedy
     void setSampling(int k, uint64_t seed = 0) { LLMI_CALL(llmi_engine_set_sampling(eng, k, seed)); }
+    // temperature / top-k / top-p / repetition-penalty sampling (llmi_engine_set_sampling_params; no
+    // reference counterpart): replaces setSampling's sampler, and setSampling replaces this one
+    void setSamplingParams(int top_k = 0, float top_p = 1.f, float temperature = 1.f, float repetition_penalty = 1.f,
+                           uint64_t seed = 0) {
+        const llmi_sampling_params p{top_k, top_p, temperature, repetition_penalty, seed};
+        LLMI_CALL(llmi_engine_set_sampling_params(eng, &p));
+    }
 
     // Greedy generation (the reference's K = 1 top-k + sampling). tokens_per_sync
     // forwards run back to back (graph replays) between host reads, so the host
@@ -229,6 +236,14 @@ public:
         }
         if (PrintRes) PrintRes(-1, res.c_str());
         return res;
+    }
+
+    // Response samples with temperature / top-k / top-p / repetition penalty instead of
+    // greedy argmax (llmi_engine_set_sampling_params; the reference has no such control)
+    void setSamplingParams(int top_k = 0, float top_p = 1.f, float temperature = 1.f, float repetition_penalty = 1.f,
+                           uint64_t seed = 0) {
+        const llmi_sampling_params p{top_k, top_p, temperature, repetition_penalty, seed};
+        LLMI_CALL(llmi_engine_set_sampling_params(eng, &p));
     }
 
     // the generated ids of the last Response (for tests and callers that keep ids)

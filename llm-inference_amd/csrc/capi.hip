@@ -339,6 +339,13 @@ int llmi_sampling(const int32_t* topk_ids, void* topk_vals, int dtype, int rows,
                            STREAM(stream));
 }
 
+int llmi_sample_nucleus(const float* logits, int rows, int vocab, const int32_t* history, int history_stride,
+                        const int32_t* history_len, float repetition_penalty, float temperature, int top_k,
+                        float top_p, uint64_t step, int32_t* out_id, int32_t* out_kept, llmi_stream_t stream) {
+    return sample_nucleus_launch(logits, rows, vocab, history, history_stride, history_len, repetition_penalty,
+                                 temperature, top_k, top_p, step, out_id, out_kept, STREAM(stream));
+}
+
 int llmi_repeat_kv(const void* k_cache, const void* v_cache, int dtype, int layer, const int32_t* context_length,
                    int batch, int kv_heads, int max_seq, int heads, int max_k_len, int head_dim, void* k_dst,
                    void* v_dst, llmi_stream_t stream) {

@@ -236,6 +236,9 @@ struct Engine {
     // stochastic sampling (Llama<T>::Sampling, llama.cpp:245-262): 0 = greedy argmax
     int sample_k = 0;
     uint64_t sample_seed = 0;
+    // llmi_engine_set_sampling_params: the nucleus sampler (nucleus.hip) instead
+    bool nuc_on = false;
+    llmi_sampling_params nuc{};
     int32_t* samp_ids = nullptr;
     float* samp_vals = nullptr;
 
@@ -888,8 +891,16 @@ struct Engine {
             h.xt_cnt = xt_cnt;
         }
         LLMI_TRY(gemv_launch(h, stream));
+        return rec_sample();
+    }
+    // the sampled id replaces the argmax partials: the nucleus sampler over the whole row
+    // (history tokens[0 .. cur_pos]: step_start / prefill_finish have written them), or
+    // top-K of this token's logits and the reference's pick
+    int rec_sample() {
+        if (nuc_on)
+            return engine_nucleus_launch(st, logits, c.vocab, tokens, nuc.repetition_penalty, nuc.temperature,
+                                         nuc.top_k, nuc.top_p, nuc.seed, partials, lm_grid, stream);
         if (sample_k == 0) return LLMI_OK;
-        // top-K of this token's logits, then the sampled id replaces the argmax partials
         LLMI_TRY(topk_launch(logits, LLMI_F32, 1, c.vocab, sample_k, samp_ids, samp_vals, stream));
         return sample_pick_launch(st, samp_ids, samp_vals, sample_k, sample_seed, partials, lm_grid, stream);
     }
@@ -995,6 +1006,17 @@ struct Engine {
         }
         sample_k = k;
         sample_seed = sd;
+        nuc_on = false;  // each of the two setters replaces the other
+        return LLMI_OK;
+    }
+    int set_sampling_params(const llmi_sampling_params& p) {
+        LLMI_REQUIRE(c.tp_world == 1 && !grouped, "set_sampling_params: sampling needs the full logits (tp_world 1)");
+        LLMI_TRY(engine_nucleus_check(c.vocab, p.repetition_penalty, p.temperature, p.top_k, p.top_p));
+        LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
+        graphs.clear();                          // the captured step changes
+        nuc = p;
+        nuc_on = true;
+        sample_k = 0;
         return LLMI_OK;
     }
 
@@ -1078,9 +1100,7 @@ struct Engine {
         GemvArgs h = lm_args();
         h.x_fixed = acc_a(c.layers);
         LLMI_TRY(gemv_launch(h, stream));
-        if (sample_k == 0) return LLMI_OK;
-        LLMI_TRY(topk_launch(logits, LLMI_F32, 1, c.vocab, sample_k, samp_ids, samp_vals, stream));
-        return sample_pick_launch(st, samp_ids, samp_vals, sample_k, sample_seed, partials, lm_grid, stream);
+        return rec_sample();
     }
 
     int record_step() {
@@ -1689,6 +1709,12 @@ int llmi_engine_set_sampling(llmi_engine* e, int k, uint64_t seed) {
     LLMI_REQUIRE(e, "null engine");
     LLMI_HIP(hipSetDevice(e->e.device));
     return e->e.set_sampling(k, seed);
+}
+
+int llmi_engine_set_sampling_params(llmi_engine* e, const llmi_sampling_params* p) {
+    LLMI_REQUIRE(e && p, "engine_set_sampling_params: null engine or params");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.set_sampling_params(*p);
 }
 
 int llmi_engine_load_bin(llmi_engine* e, const char* weight_path) {

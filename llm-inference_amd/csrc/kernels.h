@@ -471,6 +471,16 @@ int sample_pick_launch(const struct DecodeState* st, const int32_t* ids, float* 
 int topk_launch(const void* logits, int dtype, int rows, int vocab, int k, int32_t* ids, void* vals, hipStream_t s);
 int sampling_launch(const int32_t* topk_ids, void* topk_vals, int dtype, int rows, int k, int32_t* output_id,
                     int32_t* seqlen, uint8_t* is_finished, int step, int end_id, int vocab, hipStream_t s);
+// temperature / top-k / top-p / repetition-penalty sampling over whole rows (nucleus.hip)
+int sample_nucleus_launch(const float* logits, int rows, int vocab, const int32_t* history, int history_stride,
+                          const int32_t* history_len, float penalty, float temperature, int top_k, float top_p,
+                          uint64_t step, int32_t* out_id, int32_t* out_kept, hipStream_t s);
+// engine form: history tokens[0 .. cur_pos] and step = seed + cur_pos + 1 from the device
+// state, the id written as the only non-zero argmax partial (as sample_pick_launch)
+int engine_nucleus_check(int vocab, float penalty, float temperature, int top_k, float top_p);
+int engine_nucleus_launch(const struct DecodeState* st, const float* logits, int vocab, const int32_t* tokens,
+                          float penalty, float temperature, int top_k, float top_p, uint64_t seed,
+                          unsigned long long* partials, int np, hipStream_t s);
 int repeat_kv_launch(const void* k_cache, const void* v_cache, int dtype, int layer, const int* ctx_len, int batch,
                      int kv_heads, int max_seq, int heads, int max_k_len, int d, void* k_dst, void* v_dst,
                      hipStream_t s);

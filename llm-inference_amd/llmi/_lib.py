@@ -33,6 +33,12 @@ class Config(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class SamplingParams(C.Structure):
+    """llmi_sampling_params (include/llmi.h), field for field."""
+    _fields_ = [("top_k", C.c_int), ("top_p", C.c_float), ("temperature", C.c_float),
+                ("repetition_penalty", C.c_float), ("seed", C.c_uint64)]
+
+
 class DebugGemvArgs(C.Structure):
     """llmi_debug_gemv_args (include/llmi.h), field for field; pointers are device addresses."""
     _fields_ = [("w", C.c_void_p), ("scales", C.c_void_p),
@@ -79,6 +85,7 @@ _SIGS = {
     "llmi_argmax": (_I, [_P, _I, _P, _P]),
     "llmi_topk": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "llmi_sampling": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "llmi_sample_nucleus": (_I, [_P, _I, _I, _P, _I, _P, _F, _F, _I, _F, _U64, _P, _P, _P]),
     "llmi_repeat_kv": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "llmi_padding_offset": (_I, [_P, _P, _P, _I, _I, _P]),
     "llmi_rope_qkv_prefill": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
@@ -122,6 +129,7 @@ _SIGS = {
     "llmi_engine_load_synthetic": (_I, [_P, _U64]),
     "llmi_engine_load_bin": (_I, [_P, C.c_char_p]),
     "llmi_engine_set_sampling": (_I, [_P, _I, _U64]),
+    "llmi_engine_set_sampling_params": (_I, [_P, _P]),
     "llmi_engine_load_tensor": (_I, [_P, C.c_char_p, _P, _SZ]),
     "llmi_engine_load_bin_quantized": (_I, [_P, C.c_char_p]),
     "llmi_engine_load_tensor_quantized": (_I, [_P, C.c_char_p, _P, _SZ]),

@@ -69,6 +69,14 @@ class Engine:
         """Top-k stochastic sampling in the decode step (k = 0: greedy, the default)."""
         call("llmi_engine_set_sampling", self._h, int(k), int(seed))
 
+    def set_sampling_params(self, top_k: int = 0, top_p: float = 1.0, temperature: float = 1.0,
+                            repetition_penalty: float = 1.0, seed: int = 0):
+        """Temperature / top-k / top-p / repetition-penalty sampling in the token step
+        (llmi_engine_set_sampling_params; top_k = 0: no limit). Replaces set_sampling's
+        sampler; set_sampling (any k) replaces this one."""
+        p = _lib.SamplingParams(int(top_k), float(top_p), float(temperature), float(repetition_penalty), int(seed))
+        call("llmi_engine_set_sampling_params", self._h, C.byref(p))
+
     def load_bin(self, weight_path: str, quantize: bool = False):
         """Llama<T>::loadWeights(weight_path): weight_path + "<name>.bin" raw fp32 files
         (llmi/convert.py writes them); the path is used as a prefix, like the reference's.

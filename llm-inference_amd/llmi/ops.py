@@ -141,6 +141,39 @@ def launchTopKforBeamSearch(probs: torch.Tensor, k: int = 5):
     return ids, vals
 
 
+def sample_nucleus(logits: torch.Tensor, step: int, top_k: int = 0, top_p: float = 1.0, temperature: float = 1.0,
+                   repetition_penalty: float = 1.0, history: torch.Tensor = None, history_len: torch.Tensor = None,
+                   out_id: torch.Tensor = None, out_kept: torch.Tensor = None):
+    """llmi_sample_nucleus (no reference counterpart): logits [rows, vocab] (or [vocab]) fp32,
+    left unchanged; history [rows, n] int32 with history_len [rows] valid ids per row (None: all
+    n). Row b draws u = curand_uniform(curand_init(step, b, 0)). Returns (out_id, out_kept),
+    int32 [rows]: the sampled id and the size of the kept set."""
+    _dev(logits, history, history_len, out_id, out_kept)
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("sample_nucleus: logits must be contiguous float32")
+    x = logits.view(-1, logits.shape[-1])
+    rows, vocab = x.shape
+    stride = 0
+    if history is not None:
+        if history.dtype != torch.int32 or not history.is_contiguous():
+            raise ValueError("sample_nucleus: history must be contiguous int32")
+        history = history.view(rows, -1)
+        stride = history.shape[1]
+        if history_len is None:
+            history_len = torch.full((rows,), stride, device=x.device, dtype=torch.int32)
+    for t in (history_len, out_id, out_kept):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows):
+            raise ValueError("sample_nucleus: history_len, out_id and out_kept must be contiguous int32 [rows]")
+    if out_id is None:
+        out_id = torch.empty(rows, device=x.device, dtype=torch.int32)
+    if out_kept is None:
+        out_kept = torch.empty(rows, device=x.device, dtype=torch.int32)
+    call("llmi_sample_nucleus", x.data_ptr(), rows, vocab, _p(history), stride, _p(history_len),
+         float(repetition_penalty), float(temperature), int(top_k), float(top_p), int(step), out_id.data_ptr(),
+         out_kept.data_ptr(), _stream())
+    return out_id, out_kept
+
+
 def launchSampling(topk_id, topk_val, seqlen, is_finished, output_id, step: int, end_id: int, vocab_size: int):
     """In place, like the reference (sampling.cu:87-115, params step/end_id/vocab_size from
     its IntDict): topk_val <- exp(v - v[0]); output_id, seqlen, is_finished (uint8/bool)
