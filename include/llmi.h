@@ -86,7 +86,9 @@ int llmi_silu_mul(const float* gate_up, float* out, int n_tokens, int inter, llm
 
 /* launchLinearGemm (src/kernels/linear.h:16-22) with trans_b = true:
  * y[m, n] = sum_k x[m, k] * W[n, k] (* scales[n] for int8). fp32 accumulate.
- * decode (m <= 8): HBM-streaming GEMV; m > 8: batched (prefill) path. */
+ * m = 1: the HBM-streaming GEMV. 2 <= m <= 8 (and larger m on shapes the GEMM tiles do not
+ * cover, 8 rows at a time): the multi-row GEMV, which streams W once for the rows of a
+ * launch; every row is bitwise the m = 1 result for that row. m > 8: batched (prefill) path. */
 int llmi_linear(const float* x, const void* w, int w_dtype, const void* w_scales, float* y, int m,
                 int n, int k, llmi_stream_t stream);
 
@@ -205,6 +207,16 @@ typedef struct llmi_debug_gemv_args {
 } llmi_debug_gemv_args;
 int llmi_debug_gemv(const llmi_debug_gemv_args* args, llmi_stream_t stream);
 int llmi_debug_gemv_plan(const llmi_debug_gemv_args* args, int* grid, int* unroll, int* xpt);
+/* llmi_debug_gemv_rows: the multi-row GEMV of a batched decode step -- args[0 .. m), 2 <= m <= 8,
+ * are m activation rows against ONE weight matrix, streamed once. The blocks must agree in
+ * every weight-side, shape and epilogue field (w, scales, w_dtype, n_rows, k, ldw, gamma,
+ * g_dtype, eps, epi, resid_scale, pair_off, idx_base, grid, ksplit, yacc_single, seed_n,
+ * seed_keep, kpar; else LLMI_EINVAL) and differ in the per-row pointers x / x_fixed, x_out, y,
+ * resid, yacc, yacc_base, yacc_copy, partials, seed_src, seed_dst, which need not be
+ * contiguous. Row i's outputs are bitwise those of llmi_debug_gemv(&args[i]). x is fp32
+ * without RMSNorm (any epilogue) or x_fixed with RMSNorm (epi 0, 2, 3); other input forms and
+ * kpar > 1 return LLMI_EUNSUPPORTED; m outside 2..8 LLMI_EINVAL. Nothing is launched on an error. */
+int llmi_debug_gemv_rows(const llmi_debug_gemv_args* args, int m, llmi_stream_t stream);
 
 /* llmi_debug_attn_oproj: one layer's decode attention as the engine's separate launches run
  * it -- the split-KV attention leaving its partials in `workspace` (no merge kernel), then the
@@ -707,6 +719,39 @@ int llmi_group_hidden(llmi_group* g, int rank, float* out, int n);
  * push fused into every rank's o_proj / down / lm_head launch (their tails), then every
  * rank's reduce kernel (one stream: an in-launch wait for a later rank cannot finish). */
 int llmi_group_set_exchange(llmi_group* g, int mode);
+
+/* ---- Batched decode (no reference counterpart: the reference decodes one sequence). Up to
+ * 8 sequence slots share ONE copy of the weights and one stream. A step advances every
+ * active slot by one token: the q/k/v, gate_up, down and lm_head projections of all active
+ * slots run as one multi-row GEMV each (every weight streamed once per step instead of once
+ * per sequence); the attention + o_proj pair runs per slot at that slot's own position. A
+ * slot decoded in a batch gives bitwise the tokens and logits it gives alone in an engine
+ * with the same configuration, weights and sampling. Slots may hold prompts of different
+ * lengths and sit at different positions; prompts are consumed by decode steps (no batched
+ * prefill). A slot without a prompt is idle and costs nothing. Admission and eviction are the
+ * caller's: llmi_batch_set_prompt (re)starts one slot, llmi_batch_reset makes it idle.
+ * cfg->tp_world must be 1 (else LLMI_EUNSUPPORTED); n_seq in 1..8. */
+typedef struct llmi_batch llmi_batch;
+int llmi_batch_create(const llmi_config* cfg, int n_seq, int device, llmi_batch** out);
+int llmi_batch_destroy(llmi_batch* b);
+int llmi_batch_load_synthetic(llmi_batch* b, uint64_t seed);
+int llmi_batch_load_bin(llmi_batch* b, const char* weight_path);
+int llmi_batch_load_bin_quantized(llmi_batch* b, const char* weight_path);
+int llmi_batch_set_prompt(llmi_batch* b, int seq, const int32_t* ids, int n);
+int llmi_batch_reset(llmi_batch* b, int seq);
+/* llmi_engine_set_sampling_params for one slot: step = seed + the sampled token's position,
+ * row 0, as in the engine. */
+int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_params* p);
+/* Every active slot advances n_steps tokens. LLMI_EINVAL if no slot is active or any active
+ * slot would pass max_seq. use_graph: the step is captured per (active slots, their attention
+ * split counts) in a bounded cache and replayed; replay is bitwise the eager step. */
+int llmi_batch_decode(llmi_batch* b, int n_steps, int use_graph);
+int llmi_batch_tokens(llmi_batch* b, int seq, int32_t* out, int n, int* n_valid);
+int llmi_batch_logits(llmi_batch* b, int seq, float* out, int n);
+int llmi_batch_sync(llmi_batch* b);
+/* Bytes one step over the currently active slots streams: the weights once, W_o (still read
+ * per slot) once per active slot; and the KV bytes per cached position of one slot. */
+int llmi_batch_bytes(llmi_batch* b, uint64_t* weight_bytes_per_step, uint64_t* kv_bytes_per_pos);
 
 #ifdef __cplusplus
 }

@@ -145,6 +145,34 @@ int llmi_debug_gemv_plan(const llmi_debug_gemv_args* args, int* grid, int* unrol
     return gemv_plan(debug_gemv_args(*args), grid, unroll, xpt);
 }
 
+int llmi_debug_gemv_rows(const llmi_debug_gemv_args* args, int m, llmi_stream_t stream) {
+    LLMI_REQUIRE(args != nullptr, "debug_gemv_rows: null arguments");
+    LLMI_REQUIRE(m >= 2 && m <= kGemvRowsMax, "debug_gemv_rows: m must be 2..8");
+    GemvRowsArgs p;
+    p.m = m;
+    for (int i = 0; i < m; ++i) {
+        const llmi_debug_gemv_args& d = args[i];
+        const llmi_debug_gemv_args& z = args[0];
+        LLMI_REQUIRE(d.epi >= EPI_STORE && d.epi <= EPI_ATOMIC, "debug_gemv_rows: epi must be 0..4");
+        LLMI_REQUIRE(d.grid >= 0 && d.seed_n >= 0 && (!d.seed_dst || !d.seed_keep || d.seed_src),
+                     "debug_gemv_rows: bad grid or seed arguments");
+        LLMI_REQUIRE(d.w == z.w && d.scales == z.scales && d.w_dtype == z.w_dtype && d.n_rows == z.n_rows &&
+                         d.k == z.k && d.ldw == z.ldw && d.gamma == z.gamma && d.g_dtype == z.g_dtype &&
+                         d.eps == z.eps && d.epi == z.epi && d.resid_scale == z.resid_scale &&
+                         d.pair_off == z.pair_off && d.idx_base == z.idx_base && d.grid == z.grid &&
+                         d.ksplit == z.ksplit && d.yacc_single == z.yacc_single && d.seed_n == z.seed_n &&
+                         d.seed_keep == z.seed_keep && d.kpar == z.kpar,
+                     "debug_gemv_rows: the rows must share every weight-side, shape and epilogue field");
+        const GemvArgs a = debug_gemv_args(d);
+        if (i == 0) p.a = a;
+        GemvRow& r = p.row[i];
+        r.x = a.x; r.x_fixed = a.x_fixed; r.x_out = a.x_out; r.y = a.y; r.resid = a.resid;
+        r.yacc = a.yacc; r.yacc_base = a.yacc_base; r.yacc_copy = a.yacc_copy; r.partials = a.partials;
+        r.seed_src = a.seed_src; r.seed_dst = a.seed_dst;
+    }
+    return gemv_rows_launch(p, STREAM(stream));
+}
+
 int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t stream) {
     LLMI_REQUIRE(args != nullptr, "debug_attn_oproj: null arguments");
     const llmi_debug_attn_oproj_args& d = *args;
@@ -201,10 +229,24 @@ int llmi_linear(const float* x, const void* w, int w_dtype, const void* w_scales
         g.epi = EPI_STORE; g.y = y; g.ldy = n;
         return gemm_launch(g, STREAM(stream));
     }
-    for (int i = 0; i < m; ++i) {  // decode rows (and shapes the GEMM tiles do not cover): GEMV
-        a.x = x + (size_t)i * k;
-        a.y = y + (size_t)i * n;
-        LLMI_TRY(gemv_launch(a, STREAM(stream)));
+    // decode rows (and shapes the GEMM tiles do not cover): GEMV, up to 8 rows per weight stream
+    // (gemv_rows.hip: every row bitwise the single-row launch's)
+    for (int i0 = 0; i0 < m; i0 += kGemvRowsMax) {
+        const int mm = m - i0 < kGemvRowsMax ? m - i0 : kGemvRowsMax;
+        if (mm == 1) {
+            a.x = x + (size_t)i0 * k;
+            a.y = y + (size_t)i0 * n;
+            LLMI_TRY(gemv_launch(a, STREAM(stream)));
+            continue;
+        }
+        GemvRowsArgs p;
+        p.a = a;
+        p.m = mm;
+        for (int i = 0; i < mm; ++i) {
+            p.row[i].x = x + (size_t)(i0 + i) * k;
+            p.row[i].y = y + (size_t)(i0 + i) * n;
+        }
+        LLMI_TRY(gemv_rows_launch(p, STREAM(stream)));
     }
     return LLMI_OK;
 }

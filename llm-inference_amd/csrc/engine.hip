@@ -38,6 +38,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <vector>
 
@@ -268,8 +269,12 @@ struct Engine {
     }
 
     // ---------------------------------------------------------------- setup
-    // ext_stream != nullptr: rank of an in-process group (no RCCL communicator)
-    int init(const llmi_config& cfg, int dev, const void* tp_id, hipStream_t ext_stream = nullptr) {
+    // ext_stream != nullptr: rank of an in-process group (no RCCL communicator), or -- group_rank
+    // false -- a slot of a batch (struct Batch): a whole single-rank engine on the batch's stream.
+    // lender: the slot borrows that engine's weights (the Layer pointers are copied, nothing is
+    // allocated for them and nothing freed on destroy; the lender must outlive it)
+    int init(const llmi_config& cfg, int dev, const void* tp_id, hipStream_t ext_stream = nullptr,
+             const Engine* lender = nullptr, bool group_rank = true) {
         c = cfg;
         device = dev;
         const int W = c.tp_world;
@@ -301,7 +306,7 @@ struct Engine {
         if (ext_stream) {
             stream = ext_stream;
             own_stream = false;
-            grouped = true;
+            grouped = group_rank;
         } else {
             LLMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         }
@@ -315,7 +320,15 @@ struct Engine {
             ncclResult_t r = ncclCommInitRank(&comm, W, id, c.tp_rank);
             LLMI_REQUIRE(r == ncclSuccess, std::string("ncclCommInitRank: ") + ncclGetErrorString(r));
         }
-        LLMI_TRY(alloc_weights());
+        if (lender) {
+            layers = lender->layers;
+            embed = lender->embed;
+            lm_head = lender->lm_head;
+            final_norm = lender->final_norm;
+            stream_bytes = lender->stream_bytes;
+        } else {
+            LLMI_TRY(alloc_weights());
+        }
         LLMI_TRY(alloc_state());
         return LLMI_OK;
     }
@@ -1571,6 +1584,165 @@ struct Group {
     }
 };
 
+// Batched decode: n_seq sequence slots, each a whole single-rank Engine on ONE shared stream
+// that borrows slot 0's weights (its own DecodeState, token / prompt buffers, KV cache,
+// residual accumulators, q/k/v, activation, attention workspace and logits). A step over the
+// active slots runs every slot's step_start, then per layer ONE multi-row GEMV (gemv_rows.hip)
+// for q/k/v, the existing attention + o_proj launches per slot (that slot's own position and
+// split count), ONE multi-row GEMV for gate_up and ONE for down, then ONE for the lm_head and
+// each slot's sampler. The multi-row GEMV gives every row bitwise the single-row result, and
+// everything else is the engine's own launch, so a slot's tokens and logits are bitwise those
+// of an Engine decoding the sequence alone. W_o is still streamed once per slot.
+struct Batch {
+    std::vector<std::unique_ptr<Engine>> r;
+    hipStream_t stream = nullptr;
+    // captured steps by key {slot, nact, slot, nact, ...} of the active slots; bounded: a full
+    // cache is dropped whole (after a sync) before the next capture
+    static constexpr size_t kMaxGraphs = 64;
+    std::map<std::vector<int>, std::pair<hipGraph_t, hipGraphExec_t>> graphs;
+
+    void clear_graphs() {
+        for (auto& kv : graphs) {
+            if (kv.second.second) (void)hipGraphExecDestroy(kv.second.second);
+            if (kv.second.first) (void)hipGraphDestroy(kv.second.first);
+        }
+        graphs.clear();
+    }
+    ~Batch() {
+        clear_graphs();
+        while (r.size() > 1) r.pop_back();  // the borrowers before the lender
+        r.clear();
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+
+    int init(const llmi_config& cfg, int n_seq, int dev) {
+        LLMI_REQUIRE(n_seq >= 1 && n_seq <= kGemvRowsMax, "batch: n_seq must be 1..8");
+        if (cfg.tp_world != 1) {
+            set_last_error("[llmi][ERROR] batch: tensor-parallel batches are not built (tp_world must be 1)");
+            return LLMI_EUNSUPPORTED;
+        }
+        LLMI_HIP(hipSetDevice(dev));
+        LLMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        for (int i = 0; i < n_seq; ++i) {
+            r.emplace_back(new Engine());
+            LLMI_TRY(r.back()->init(cfg, dev, nullptr, stream, i ? r[0].get() : nullptr, false));
+        }
+        return LLMI_OK;
+    }
+    int slot_ok(int seq) const {
+        LLMI_REQUIRE(seq >= 0 && seq < (int)r.size(), "batch: seq out of range");
+        return LLMI_OK;
+    }
+    int drop_graphs() {
+        if (!graphs.empty()) {
+            LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
+            clear_graphs();
+        }
+        return LLMI_OK;
+    }
+    int loaded() {  // slot 0 holds the weights every slot reads
+        for (size_t i = 1; i < r.size(); ++i) r[i]->seed = r[0]->seed;
+        return drop_graphs();
+    }
+    int reset(int seq) {
+        LLMI_TRY(slot_ok(seq));
+        LLMI_HIP(hipStreamSynchronize(stream));
+        r[seq]->prompt_len = 0;
+        r[seq]->host_next_pos = 0;
+        return LLMI_OK;
+    }
+    std::vector<int> active() const {
+        std::vector<int> a;
+        for (int i = 0; i < (int)r.size(); ++i)
+            if (r[i]->prompt_len > 0) a.push_back(i);
+        return a;
+    }
+
+    // one multi-row GEMV from the active slots' own single-row arguments
+    template <typename F>
+    int rows(const std::vector<int>& act, F&& args_of) {
+        GemvRowsArgs p;
+        p.m = (int)act.size();
+        for (int i = 0; i < p.m; ++i) {
+            const GemvArgs a = args_of(*r[act[i]]);
+            if (i == 0) p.a = a;
+            GemvRow& w = p.row[i];
+            w.x = a.x; w.x_fixed = a.x_fixed; w.x_out = a.x_out; w.y = a.y; w.resid = a.resid;
+            w.yacc = a.yacc; w.yacc_base = a.yacc_base; w.yacc_copy = a.yacc_copy; w.partials = a.partials;
+            w.seed_src = a.seed_src; w.seed_dst = a.seed_dst;
+        }
+        return gemv_rows_launch(p, stream);
+    }
+
+    // one step of the active slots; every slot's rec_nact is set
+    int record_step(const std::vector<int>& act) {
+        for (int s : act) LLMI_TRY(r[s]->rec_start());
+        const int L = r[0]->c.layers;
+        if (act.size() == 1) {  // one sequence: the engine's own single-row launches
+            Engine& e = *r[act[0]];
+            for (int l = 0; l < L; ++l) {
+                LLMI_TRY(e.rec_attn(l));
+                LLMI_TRY(e.rec_ffn(l));
+            }
+            return e.rec_head();
+        }
+        for (int l = 0; l < L; ++l) {
+            LLMI_TRY(rows(act, [&](Engine& e) { return e.qkv_args(l); }));
+            for (int s : act) {
+                Engine& e = *r[s];
+                const AttnArgs at = e.attn_args(l);
+                LLMI_TRY(e.rec_oproj(LLMI_OK, e.o_args(l), &at));
+            }
+            LLMI_TRY(rows(act, [&](Engine& e) { return e.gu_args(l); }));
+            LLMI_TRY(rows(act, [&](Engine& e) { return e.down_args(l); }));
+        }
+        LLMI_TRY(rows(act, [&](Engine& e) { return e.lm_args(); }));
+        for (int s : act) LLMI_TRY(r[s]->rec_sample());
+        return LLMI_OK;
+    }
+
+    int decode(int n, int use_graph) {
+        const std::vector<int> act = active();
+        LLMI_REQUIRE(!act.empty(), "batch decode: no active slot (set_prompt first)");
+        LLMI_REQUIRE(n >= 0, "batch decode: n_steps must be >= 0");
+        for (int s : act)
+            LLMI_REQUIRE(r[s]->host_next_pos + n <= r[s]->c.max_seq, "batch decode: a slot would run past max_seq");
+        for (int i = 0; i < n; ++i) {
+            std::vector<int> key;
+            for (int s : act) {
+                r[s]->rec_nact = Engine::nact_of(r[s]->host_next_pos + i);
+                key.push_back(s);
+                key.push_back(r[s]->rec_nact);
+            }
+            if (!use_graph) {
+                LLMI_TRY(record_step(act));
+                continue;
+            }
+            auto it = graphs.find(key);
+            if (it == graphs.end()) {
+                if (graphs.size() >= kMaxGraphs) LLMI_TRY(drop_graphs());
+                LLMI_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
+                const int rc = record_step(act);
+                hipGraph_t h = nullptr;
+                const hipError_t e = hipStreamEndCapture(stream, &h);
+                if (rc != LLMI_OK) {
+                    if (h) (void)hipGraphDestroy(h);
+                    return rc;
+                }
+                LLMI_HIP(e);
+                hipGraphExec_t x = nullptr;
+                const hipError_t ei = hipGraphInstantiate(&x, h, nullptr, nullptr, 0);
+                if (ei != hipSuccess) (void)hipGraphDestroy(h);
+                LLMI_HIP(ei);
+                it = graphs.emplace(key, std::make_pair(h, x)).first;
+            }
+            LLMI_HIP(hipGraphLaunch(it->second.second, stream));
+        }
+        for (int s : act) r[s]->host_next_pos += n;
+        return LLMI_OK;
+    }
+};
+
 }  // namespace llmi
 
 // ============================================================== C ABI (engine)
@@ -1584,6 +1756,9 @@ struct llmi_engine {
 };
 struct llmi_group {
     llmi::Group g;
+};
+struct llmi_batch {
+    llmi::Batch b;
 };
 
 namespace {
@@ -2142,6 +2317,113 @@ int llmi_group_hidden(llmi_group* g, int rank, float* out, int n) {
                  "group_hidden: bad arguments");
     LLMI_HIP(hipStreamSynchronize(g->g.stream));
     LLMI_HIP(hipMemcpy(out, g->g.r[rank]->x, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return LLMI_OK;
+}
+
+// ---- batched decode (struct Batch)
+int llmi_batch_create(const llmi_config* cfg, int n_seq, int device, llmi_batch** out) {
+    LLMI_REQUIRE(cfg && out, "batch_create: null argument");
+    *out = nullptr;
+    auto h = std::make_unique<llmi_batch>();
+    int rc = h->b.init(*cfg, n_seq, device);
+    if (rc != LLMI_OK) return rc;
+    *out = h.release();
+    return LLMI_OK;
+}
+
+int llmi_batch_destroy(llmi_batch* b) {
+    if (b) {
+        (void)hipSetDevice(b->b.r.empty() ? 0 : b->b.r[0]->device);
+        if (b->b.stream) (void)hipStreamSynchronize(b->b.stream);
+        delete b;
+    }
+    return LLMI_OK;
+}
+
+int llmi_batch_load_synthetic(llmi_batch* b, uint64_t seed) {
+    LLMI_REQUIRE(b, "null batch");
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    LLMI_TRY(b->b.r[0]->load_synthetic(seed));
+    return b->b.loaded();
+}
+
+int llmi_batch_load_bin(llmi_batch* b, const char* weight_path) {
+    LLMI_REQUIRE(b, "null batch");
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    LLMI_TRY(b->b.r[0]->load_bin(weight_path));
+    return b->b.loaded();
+}
+
+int llmi_batch_load_bin_quantized(llmi_batch* b, const char* weight_path) {
+    LLMI_REQUIRE(b, "null batch");
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    LLMI_TRY(b->b.r[0]->load_bin(weight_path, true));
+    return b->b.loaded();
+}
+
+int llmi_batch_set_prompt(llmi_batch* b, int seq, const int32_t* ids, int n) {
+    LLMI_REQUIRE(b, "null batch");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    return b->b.r[seq]->set_prompt(ids, n);
+}
+
+int llmi_batch_reset(llmi_batch* b, int seq) {
+    LLMI_REQUIRE(b, "null batch");
+    return b->b.reset(seq);
+}
+
+int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_params* p) {
+    LLMI_REQUIRE(b && p, "batch_set_sampling_params: null batch or params");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    LLMI_TRY(b->b.r[seq]->set_sampling_params(*p));
+    return b->b.drop_graphs();  // the captured steps change
+}
+
+int llmi_batch_decode(llmi_batch* b, int n_steps, int use_graph) {
+    LLMI_REQUIRE(b, "null batch");
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    return b->b.decode(n_steps, use_graph);
+}
+
+int llmi_batch_tokens(llmi_batch* b, int seq, int32_t* out, int n, int* n_valid) {
+    LLMI_REQUIRE(b && (out || n == 0), "batch_tokens: null argument");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    if (b->b.r[seq]->prompt_len == 0) {  // idle: no sequence
+        if (n_valid) *n_valid = 0;
+        return LLMI_OK;
+    }
+    return b->b.r[seq]->tokens_out(out, n, n_valid);
+}
+
+int llmi_batch_logits(llmi_batch* b, int seq, float* out, int n) {
+    LLMI_REQUIRE(b && out, "batch_logits: null argument");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_REQUIRE(n >= 0 && n <= b->b.r[seq]->vl, "batch_logits: n exceeds the vocabulary");
+    LLMI_HIP(hipStreamSynchronize(b->b.stream));
+    LLMI_HIP(hipMemcpy(out, b->b.r[seq]->logits, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return LLMI_OK;
+}
+
+int llmi_batch_sync(llmi_batch* b) {
+    LLMI_REQUIRE(b, "null batch");
+    LLMI_HIP(hipStreamSynchronize(b->b.stream));
+    return LLMI_OK;
+}
+
+int llmi_batch_bytes(llmi_batch* b, uint64_t* weight_bytes_per_step, uint64_t* kv_bytes_per_pos) {
+    LLMI_REQUIRE(b, "null batch");
+    const Engine& g = *b->b.r[0];
+    const uint64_t n_act = b->b.active().size();
+    // the weights once; W_o (+ its int8 row scales) once more for every further active slot
+    uint64_t wo = (uint64_t)g.c.hidden * g.ql * g.wsz;
+    if (g.wdt == LLMI_I8) wo += (uint64_t)g.c.hidden * 2;
+    if (weight_bytes_per_step)
+        *weight_bytes_per_step = g.stream_bytes + (n_act > 1 ? (n_act - 1) * wo * g.c.layers : 0);
+    if (kv_bytes_per_pos)
+        *kv_bytes_per_pos = (uint64_t)g.c.layers * g.kvl * g.c.head_dim * 2 * llmi::dtype_size(g.c.kv_dtype);
     return LLMI_OK;
 }
 

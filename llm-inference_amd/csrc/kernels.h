@@ -101,6 +101,38 @@ int gemv_grid(const GemvArgs& a);  // blocks gemv_launch will use
 // x-staging width XPT (gemv_impl.h), from the functions the launcher itself calls
 int gemv_plan(const GemvArgs& a, int* grid, int* unroll, int* xpt);
 
+// ------------------------------------------------ multi-row GEMV (gemv_rows.hip)
+// m activation rows (2..kGemvRowsMax) against ONE weight matrix in one launch: every 16-B
+// weight chunk is loaded once and dotted against all m staged x images. Row i of the result
+// is bitwise what gemv_launch gives for row i alone (same lane-to-chunk map, same order).
+constexpr int kGemvRowsMax = 8;
+struct GemvRow {  // what differs between the activation rows (GemvArgs' fields of the same names)
+    const float* x = nullptr;
+    const long long* x_fixed = nullptr;
+    float* x_out = nullptr;
+    float* y = nullptr;
+    const float* resid = nullptr;
+    long long* yacc = nullptr;
+    const long long* yacc_base = nullptr;
+    long long* yacc_copy = nullptr;
+    unsigned long long* partials = nullptr;
+    const long long* seed_src = nullptr;
+    long long* seed_dst = nullptr;
+};
+struct GemvRowsArgs {
+    GemvArgs a;  // the weight side, the shapes and the epilogue; its per-row pointers are unused
+    int m = 0;
+    GemvRow row[kGemvRowsMax];
+};
+// the single-row arguments of activation row i (what the row's result is defined by)
+GemvArgs gemv_rows_single(const GemvRowsArgs& p, int i);
+// LLMI_EUNSUPPORTED: kpar > 1, granule rows, a fused exchange tail, stamps, or an input form the
+// token step does not run (an fp32 x with RMSNorm; a fixed-point x with the add / atomic epilogues)
+int gemv_rows_launch(const GemvRowsArgs& p, hipStream_t s);
+// activation rows one launch takes for this k (the x images must fit the LDS); more rows
+// are run as several launches
+int gemv_rows_fit(const GemvArgs& a);
+
 // ------------------------------------------------------ prefill GEMM (MFMA)
 // Y[m, n] (op)= sum_k A[m, k] W[n, k] for M prompt rows; see gemm.hip.
 struct GemmArgs {

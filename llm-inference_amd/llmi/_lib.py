@@ -103,6 +103,7 @@ _SIGS = {
     "llmi_stream_errors": (_I, [_P, _P]),
     "llmi_debug_stream_k": (_I, [_I, _I]),
     "llmi_debug_gemv": (_I, [C.POINTER(DebugGemvArgs), _P]),
+    "llmi_debug_gemv_rows": (_I, [C.POINTER(DebugGemvArgs), _I, _P]),
     "llmi_debug_gemv_plan": (_I, [C.POINTER(DebugGemvArgs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "llmi_debug_attn_oproj": (_I, [C.POINTER(DebugAttnOprojArgs), _P]),
     "llmi_debug_prefill_stamps": (_I, [_P]),
@@ -165,6 +166,19 @@ _SIGS = {
     "llmi_group_tokens": (_I, [_P, _I, _P, _I, C.POINTER(_I)]),
     "llmi_group_logits": (_I, [_P, _P, _I]),
     "llmi_group_hidden": (_I, [_P, _I, _P, _I]),
+    "llmi_batch_create": (_I, [C.POINTER(Config), _I, _I, C.POINTER(_P)]),
+    "llmi_batch_destroy": (_I, [_P]),
+    "llmi_batch_load_synthetic": (_I, [_P, _U64]),
+    "llmi_batch_load_bin": (_I, [_P, C.c_char_p]),
+    "llmi_batch_load_bin_quantized": (_I, [_P, C.c_char_p]),
+    "llmi_batch_set_prompt": (_I, [_P, _I, _P, _I]),
+    "llmi_batch_reset": (_I, [_P, _I]),
+    "llmi_batch_set_sampling_params": (_I, [_P, _I, _P]),
+    "llmi_batch_decode": (_I, [_P, _I, _I]),
+    "llmi_batch_tokens": (_I, [_P, _I, _P, _I, C.POINTER(_I)]),
+    "llmi_batch_logits": (_I, [_P, _I, _P, _I]),
+    "llmi_batch_sync": (_I, [_P]),
+    "llmi_batch_bytes": (_I, [_P, C.POINTER(_U64), C.POINTER(_U64)]),
 }
 
 _lib = None

@@ -264,3 +264,106 @@ class TPGroup:
         call("llmi_group_set_prompt", self._h, prompt.ctypes.data, len(prompt))
         call("llmi_group_decode", self._h, len(prompt) + n_new - 1, 1 if use_graph else 0)
         return self.tokens(0, len(prompt) + n_new)[len(prompt):]
+
+
+class Batch:
+    """Batched decode (llmi_batch_* in include/llmi.h): up to 8 sequence slots over one copy
+    of the weights, stepped together -- every weight but W_o is streamed once per step for all
+    active slots. A slot's tokens and logits are bitwise those of an Engine decoding the same
+    sequence alone. Admission and eviction are the caller's (set_prompt / reset)."""
+
+    def __init__(self, cfg: Config, n_seq: int, device: int = 0):
+        self.cfg, self.n_seq = cfg, n_seq
+        h = C.c_void_p()
+        call("llmi_batch_create", C.byref(cfg), n_seq, device, C.byref(h))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().llmi_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def load_synthetic(self, seed: int):
+        call("llmi_batch_load_synthetic", self._h, seed)
+
+    def load_bin(self, weight_path: str, quantize: bool = False):
+        call("llmi_batch_load_bin_quantized" if quantize else "llmi_batch_load_bin", self._h,
+             weight_path.encode())
+
+    def set_prompt(self, seq: int, ids):
+        """(Re)start slot seq with this prompt; the other slots are left where they are."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        call("llmi_batch_set_prompt", self._h, int(seq), ids.ctypes.data, len(ids))
+
+    def reset(self, seq: int):
+        """Make slot seq idle (its buffers keep their contents)."""
+        call("llmi_batch_reset", self._h, int(seq))
+
+    def set_sampling_params(self, seq: int, top_k: int = 0, top_p: float = 1.0, temperature: float = 1.0,
+                            repetition_penalty: float = 1.0, seed: int = 0):
+        p = _lib.SamplingParams(int(top_k), float(top_p), float(temperature), float(repetition_penalty), int(seed))
+        call("llmi_batch_set_sampling_params", self._h, int(seq), C.byref(p))
+
+    def decode(self, n_steps: int, use_graph: bool = True):
+        """Every active slot advances n_steps tokens."""
+        call("llmi_batch_decode", self._h, int(n_steps), 1 if use_graph else 0)
+
+    def sync(self):
+        call("llmi_batch_sync", self._h)
+
+    def tokens(self, seq: int, n: Optional[int] = None) -> np.ndarray:
+        n = self.cfg.max_seq + 1 if n is None else n
+        out = np.zeros(n, np.int32)
+        valid = C.c_int()
+        call("llmi_batch_tokens", self._h, int(seq), out.ctypes.data, n, C.byref(valid))
+        return out[:min(n, valid.value)]
+
+    def logits(self, seq: int) -> np.ndarray:
+        out = np.zeros(self.cfg.vocab, np.float32)
+        call("llmi_batch_logits", self._h, int(seq), out.ctypes.data, self.cfg.vocab)
+        return out
+
+    def bytes_per_step(self):
+        """(weight bytes one step over the active slots streams, KV bytes per position and slot)."""
+        w, kv = C.c_uint64(), C.c_uint64()
+        call("llmi_batch_bytes", self._h, C.byref(w), C.byref(kv))
+        return w.value, kv.value
+
+    def generate(self, prompts, n_new: int, use_graph: bool = True) -> list:
+        """Greedy (or each slot's sampler): slot i takes prompts[i] (None: idle) and produces
+        n_new tokens; prompts are consumed by decode steps. A slot that has its n_new tokens
+        goes idle while longer prompts finish. Returns one id array per slot (None: idle)."""
+        if len(prompts) > self.n_seq:
+            raise ValueError("generate: more prompts than slots")
+        left, out = {}, [None] * len(prompts)
+        for i in range(self.n_seq):
+            self.reset(i)
+        for i, p in enumerate(prompts):
+            if p is None:
+                continue
+            p = np.ascontiguousarray(p, np.int32)
+            self.set_prompt(i, p)
+            left[i] = len(p) + n_new - 1
+        plen = {i: len(prompts[i]) for i in left}
+        while left:
+            n = min(left.values())
+            self.decode(n, use_graph)
+            for i in list(left):
+                left[i] -= n
+                if left[i] == 0:
+                    out[i] = self.tokens(i, plen[i] + n_new)[plen[i]:]
+                    self.reset(i)
+                    del left[i]
+        return out

@@ -432,6 +432,18 @@ def debug_gemv(**fields) -> None:
     call("llmi_debug_gemv", ctypes.byref(a), _stream())
 
 
+def debug_gemv_rows(rows) -> None:
+    """llmi_debug_gemv_rows (test hook): ONE multi-row GEMV launch for the activation rows in
+    `rows`, a list of debug_gemv keyword dicts that share every weight-side field and differ in
+    the per-row buffers. Row i's outputs are bitwise debug_gemv(**rows[i])'s."""
+    arr = (_lib.DebugGemvArgs * max(len(rows), 1))()
+    for i, fields in enumerate(rows):
+        fields = dict(fields)
+        fields.setdefault("resid_scale", 1.0)
+        arr[i] = _debug_args(_lib.DebugGemvArgs, fields)
+    call("llmi_debug_gemv_rows", arr, len(rows), _stream())
+
+
 def debug_gemv_plan(**fields):
     """llmi_debug_gemv_plan (test hook): (grid, unroll, xpt) llmi_debug_gemv would use for the
     same keywords; launches nothing."""
