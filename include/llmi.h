@@ -257,6 +257,64 @@ int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t 
  * end, __smid(), then query block | head << 16, key blocks). Null turns it off. */
 int llmi_debug_prefill_stamps(void* stamps);
 
+/* Test hooks for the prefill path's own kernels (no reference counterpart; test-only: no
+ * engine or operator path calls them). llmi_engine_prefill is the only other way to these
+ * kernels, and it fixes their shapes and chunking.
+ *
+ * llmi_debug_prefill_attn: one launch of the prefill attention -- rope + cache write of rows
+ * [p0, p0 + m), then causal attention of those rows over cache slots [0, p0 + row] -- with
+ * the launcher's argument block filled field for field (zero / NULL: not used; head_dim 0 ->
+ * 128). qkv [m, (heads + 2 kv_heads) * 128] fp32, q rotated in place; qkv2: optional second
+ * summand of the same layout; k_cache / v_cache: one layer [kv_heads, max_seq, 128] of
+ * cache_dtype (f16 / f32); rope_tab [max_seq][64] (cos, sin) fp32 pairs; out [m, heads * 128].
+ * mfma_planes 0: the scalar kernel; 1 / 2 (fp16 cache): the MFMA kernel with that many fp16
+ * planes, its output in `out` or, with out_hi (, out_lo), as fp16 planes [m, heads * 128]
+ * (out_lo8: out_lo rows hold e4m3 bytes of lo * 2^12 in their first half). split_ws
+ * (split_ws_floats fp32 elements): scratch for split-key partials; chunk_blocks > 0 with
+ * split_ws: 64-key blocks per chunk instead of the automatic choice. The caller owns every buffer.
+ * llmi_debug_prefill_attn_plan launches nothing: it runs the same argument checks and the
+ * function the launcher takes its plan from, and reports the key blocks per chunk (cb), the
+ * chunk slots per query block (maxc; 1: no partials), the attention kernel's workgroup count
+ * and the merge kernel's slot count (0: no merge launch, else 2, 4 or 8). The scalar form
+ * reports cb 0, maxc 1, merge_slots 0. */
+typedef struct llmi_debug_prefill_attn_args {
+    float* qkv;
+    const float* qkv2;
+    void* k_cache;
+    void* v_cache;
+    int cache_dtype, max_seq;
+    int m, p0;
+    int heads, kv_heads, head_dim;
+    const float* rope_tab;
+    float* out;
+    int mfma_planes;
+    void* out_hi;
+    void* out_lo;
+    int out_lo8;
+    float* split_ws;
+    size_t split_ws_floats;
+    int chunk_blocks;
+} llmi_debug_prefill_attn_args;
+int llmi_debug_prefill_attn(const llmi_debug_prefill_attn_args* args, llmi_stream_t stream);
+int llmi_debug_prefill_attn_plan(const llmi_debug_prefill_attn_args* args, int* cb, int* maxc, int* grid,
+                                 int* merge_slots);
+
+/* llmi_debug_rows_split: the prefill GEMMs' activation producer. Rows of x [m, ldx] (k used):
+ * with slab [ksplit][m][k] (ldx == k) x += slice 0 + slice 1 + ... in that order, written
+ * back; then optional RMSNorm (gamma [k] of g_dtype f16 / f32; NULL: none); then fp16 planes
+ * hi = fp16(v), lo = fp16(v - hi) in rows of ldh elements (lo NULL: hi alone; lo8: the first
+ * ldh bytes of each lo row hold e4m3(clamp((v - hi) * 2^12, +-448)) instead; hi NULL with a
+ * slab: the combine alone). k a multiple of 4, at most 8192. */
+int llmi_debug_rows_split(float* x, int ldx, int m, int k, const void* gamma, int g_dtype, float eps, void* hi,
+                          void* lo, int ldh, const float* slab, int ksplit, int lo8, llmi_stream_t stream);
+
+/* llmi_debug_w8_prepare: the fp8 weight copy of the prefill GEMMs. w16 fp16 [rows, cols]
+ * (cols a multiple of 8, 16-B aligned) -> w8 rows of 2 cols bytes whose first cols bytes are
+ * e4m3(clamp(W * 2^exp, +-448)), the rest untouched; *exp (host) = the largest e with
+ * max |W| * 2^e <= 448, 0 when the maximum is zero or not finite (a NaN or an infinity in W;
+ * a NaN element stays a NaN byte). Synchronises the stream. */
+int llmi_debug_w8_prepare(const void* w16, int rows, int cols, void* w8, int* exp, llmi_stream_t stream);
+
 /* One decode row through the HBM-streaming GEMV with its fused prologue/epilogue -- what
  * LlamaSelfDecoder::forward strings together for a token (self_decoder.cpp:59-81 fused):
  *   gamma != NULL: x is RMS-normalised and scaled by gamma (dtype gamma_dtype) first;

@@ -207,6 +207,46 @@ int llmi_debug_prefill_stamps(void* stamps) {
     return LLMI_OK;
 }
 
+namespace {
+PrefillAttnArgs debug_prefill_attn_args(const llmi_debug_prefill_attn_args& d) {
+    PrefillAttnArgs a;
+    a.qkv = d.qkv; a.qkv2 = d.qkv2; a.k_cache = d.k_cache; a.v_cache = d.v_cache;
+    a.cache_dtype = d.cache_dtype; a.max_seq = d.max_seq; a.m = d.m; a.p0 = d.p0;
+    a.heads = d.heads; a.kv_heads = d.kv_heads; a.head_dim = d.head_dim ? d.head_dim : 128;
+    a.rope_tab = d.rope_tab; a.out = d.out; a.mfma_planes = d.mfma_planes;
+    a.out_hi = static_cast<_Float16*>(d.out_hi); a.out_lo = static_cast<_Float16*>(d.out_lo);
+    a.out_lo8 = d.out_lo8; a.split_ws = d.split_ws; a.split_ws_floats = d.split_ws_floats;
+    a.chunk_blocks = d.chunk_blocks;
+    return a;
+}
+}  // namespace
+
+int llmi_debug_prefill_attn(const llmi_debug_prefill_attn_args* args, llmi_stream_t stream) {
+    LLMI_REQUIRE(args != nullptr, "debug_prefill_attn: null arguments");
+    LLMI_REQUIRE(args->chunk_blocks >= 0, "debug_prefill_attn: chunk_blocks must be >= 0");
+    return prefill_attn_launch(debug_prefill_attn_args(*args), STREAM(stream));
+}
+
+int llmi_debug_prefill_attn_plan(const llmi_debug_prefill_attn_args* args, int* cb, int* maxc, int* grid,
+                                 int* merge_slots) {
+    LLMI_REQUIRE(args != nullptr && cb && maxc && grid && merge_slots, "debug_prefill_attn_plan: null arguments");
+    LLMI_REQUIRE(args->chunk_blocks >= 0, "debug_prefill_attn_plan: chunk_blocks must be >= 0");
+    PrefillAttnPlan p;
+    LLMI_TRY(prefill_attn_plan(debug_prefill_attn_args(*args), &p));
+    *cb = p.cb; *maxc = p.maxc; *grid = p.grid; *merge_slots = p.merge_slots;
+    return LLMI_OK;
+}
+
+int llmi_debug_rows_split(float* x, int ldx, int m, int k, const void* gamma, int g_dtype, float eps, void* hi,
+                          void* lo, int ldh, const float* slab, int ksplit, int lo8, llmi_stream_t stream) {
+    return rows_split_launch(x, ldx, m, k, gamma, g_dtype, eps, static_cast<_Float16*>(hi), static_cast<_Float16*>(lo),
+                             ldh, STREAM(stream), slab, ksplit, lo8 != 0);
+}
+
+int llmi_debug_w8_prepare(const void* w16, int rows, int cols, void* w8, int* exp, llmi_stream_t stream) {
+    return w8_prepare(w16, rows, cols, w8, exp, STREAM(stream));
+}
+
 int llmi_linear(const float* x, const void* w, int w_dtype, const void* w_scales, float* y, int m, int n, int k,
                 llmi_stream_t stream) {
     LLMI_REQUIRE(m >= 1 && n >= 1 && k >= 1, "linear: m, n, k must be >= 1");

@@ -795,6 +795,7 @@ int launch_sk(const Gemm2Args& a, hipStream_t s) {
 
 __global__ void w8_amax_kernel(const __half* w, size_t n, unsigned* amax) {  // n % 8 == 0, 16-B aligned
     float m = 0.f;
+    bool nan = false;  // fmaxf drops a NaN: it is carried on the side and makes the maximum a NaN
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n / 8; i += (size_t)gridDim.x * blockDim.x) {
         const uint4 u = reinterpret_cast<const uint4*>(w)[i];
         const __half2* h = reinterpret_cast<const __half2*>(&u);
@@ -802,9 +803,11 @@ __global__ void w8_amax_kernel(const __half* w, size_t n, unsigned* amax) {  // 
         for (int j = 0; j < 4; ++j) {
             const float2 f = __half22float2(h[j]);
             m = fmaxf(m, fmaxf(fabsf(f.x), fabsf(f.y)));
+            nan = nan || f.x != f.x || f.y != f.y;
         }
     }
     m = wave_max(m);
+    if (__builtin_amdgcn_ballot_w64(nan) != 0) m = __uint_as_float(0x7FC00000u);  // orders above +inf as a uint
     if ((threadIdx.x & 63) == 0) atomicMax(amax, __float_as_uint(m));  // non-negative floats order as uints
 }
 // row r of the fp16 [rows, cols] weight -> the first cols bytes of e4m3 row r (stride 2 cols bytes)
@@ -816,8 +819,8 @@ __global__ void w8_convert_kernel(const __half* w, size_t n8, int cols8, float s
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const float2 p = __half22float2(h[j]);
-            f[2 * j] = fminf(fmaxf(p.x * scale, -448.f), 448.f);
-            f[2 * j + 1] = fminf(fmaxf(p.y * scale, -448.f), 448.f);
+            f[2 * j] = p.x != p.x ? p.x : fminf(fmaxf(p.x * scale, -448.f), 448.f);  // a NaN stays a NaN byte
+            f[2 * j + 1] = p.y != p.y ? p.y : fminf(fmaxf(p.y * scale, -448.f), 448.f);
         }
         uint2 q;
         q.x = (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], 0, false), true);

@@ -284,8 +284,19 @@ struct PrefillAttnArgs {
     // MFMA form: scratch for the split-key partials (null: one workgroup per query block)
     float* split_ws = nullptr;
     size_t split_ws_floats = 0;
+    // > 0 with split_ws: key blocks (64 keys) per chunk instead of the automatic choice (as
+    // LLMI_PF_CHUNK; llmi_debug_prefill_attn). The engine leaves it 0.
+    int chunk_blocks = 0;
 };
 int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s);
+// what prefill_attn_launch would run for a, nothing launched (the launcher calls it too): cb
+// key blocks per chunk, maxc chunk slots per query block (1: no partials), the attention
+// kernel's workgroups and the merge instance (0: no merge launch, else 2, 4 or 8 slots). The
+// scalar form (mfma_planes 0) reports cb 0, maxc 1, merge_slots 0.
+struct PrefillAttnPlan {
+    int cb = 0, maxc = 1, grid = 0, merge_slots = 0;
+};
+int prefill_attn_plan(const PrefillAttnArgs& a, PrefillAttnPlan* p);
 // after a prefill of prompt rows [p0, p0 + n): record them as tokens and
 // advance the decode state (next_pos = p0 + n)
 int prefill_finish_launch(struct DecodeState* st, const int32_t* prompt, int32_t* tokens, int p0, int n,

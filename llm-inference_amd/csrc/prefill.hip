@@ -647,6 +647,9 @@ __global__ __launch_bounds__(kThreads) void attn_prefill_merge_kernel(const floa
         const float inv = 1.0f / L;
         const size_t idx = (size_t)row * ldo + (size_t)h * D + d0;
         if (out_hi) {
+            // v is the rounded fp32 product, as the fp32 output stores it: contracted into
+            // fma(acc, inv, -hi) the remainder would be that of a different v
+#pragma clang fp contract(off)
             h8 hv, lv;
             float r[8];
 #pragma unroll
@@ -689,7 +692,8 @@ int prefill_finish_launch(DecodeState* st, const int32_t* prompt, int32_t* token
 static std::atomic<unsigned long long*> g_pf_stamps{nullptr};
 void prefill_stamps_debug(unsigned long long* stamps) { g_pf_stamps.store(stamps); }
 
-int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
+namespace {
+int prefill_attn_check(const PrefillAttnArgs& a) {
     LLMI_REQUIRE(a.qkv && a.k_cache && a.v_cache && a.rope_tab, "prefill attention: null argument");
     LLMI_REQUIRE(a.head_dim == D, "prefill attention: head_dim must be 128");
     LLMI_REQUIRE(a.m > 0 && a.p0 >= 0 && a.p0 + a.m <= a.max_seq, "prefill attention: rows past max_seq");
@@ -698,44 +702,77 @@ int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
                                         (a.out || a.out_hi)),
                  "prefill attention: the MFMA form needs the fp16 cache, 1 or 2 planes and an output");
     LLMI_REQUIRE(a.mfma_planes != 0 || a.out, "prefill attention: null output");
+    LLMI_REQUIRE(a.cache_dtype == LLMI_F16 || a.cache_dtype == LLMI_F32,
+                 "prefill attention: cache dtype must be f16 or f32");
+    return LLMI_OK;
+}
+}  // namespace
+
+// the launcher's choices for a (checked arguments): key blocks per chunk, chunk slots per
+// query block, the attention grid and the merge instance. The scalar form has no chunks.
+int prefill_attn_plan(const PrefillAttnArgs& a, PrefillAttnPlan* p) {
+    LLMI_REQUIRE(p != nullptr, "prefill attention plan: null output");
+    LLMI_TRY(prefill_attn_check(a));
+    if (!a.mfma_planes) {
+        p->cb = 0;
+        p->maxc = 1;
+        p->grid = ((a.m + QB - 1) / QB) * a.heads;
+        p->merge_slots = 0;
+        return LLMI_OK;
+    }
+    // split keys: chunks of cb key blocks
+    const int nqb = (a.m + QM - 1) / QM;
+    int blocks = 0, max_nkb = 0;
+    for (int qb = 0; qb < nqb; ++qb) {
+        blocks += pf_nkb(qb, a.p0, a.m);
+        max_nkb = std::max(max_nkb, pf_nkb(qb, a.p0, a.m));
+    }
+    // one 8-wave workgroup per CU (128 KB of LDS): whole query blocks when they give
+    // every CU one; otherwise chunks of cb key blocks sized for ~one workgroup per CU
+    static const int n_cu = [] {
+        int dev = 0, n = 256;
+        if (hipGetDevice(&dev) == hipSuccess)
+            (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        else
+            (void)hipGetLastError();
+        return n > 0 ? n : 256;
+    }();
+    int cb = max_nkb;
+    if (a.split_ws && nqb * a.heads < n_cu) cb = std::max(1, (blocks * a.heads + n_cu - 1) / n_cu);
+    static const int cb_env = [] {  // tuning knob: key blocks per chunk (LLMI_PF_CHUNK)
+        const char* e = std::getenv("LLMI_PF_CHUNK");
+        return e ? std::atoi(e) : 0;
+    }();
+    if (a.split_ws && cb_env > 0) cb = cb_env;
+    if (a.split_ws && a.chunk_blocks > 0) cb = a.chunk_blocks;  // test hook; the engine leaves it 0
+    int maxc = (max_nkb + cb - 1) / cb;
+    if (a.split_ws && (maxc > 8 || (size_t)a.heads * nqb * maxc * kPartFloats > a.split_ws_floats)) {
+        cb = max_nkb;  // no room: one chunk per query block
+        maxc = 1;
+    }
+    if (!a.split_ws) cb = max_nkb, maxc = 1;
+    int items = 0;
+    for (int qb = 0; qb < nqb; ++qb) items += (pf_nkb(qb, a.p0, a.m) + cb - 1) / cb;
+    p->cb = cb;
+    p->maxc = maxc;
+    // 1-D, XCD-interleaved: 8 x ceil(heads / 8) x (items per head) workgroups
+    p->grid = 8 * ((a.heads + 7) / 8) * items;
+    p->merge_slots = maxc <= 1 ? 0 : maxc <= 2 ? 2 : maxc <= 4 ? 4 : 8;
+    return LLMI_OK;
+}
+
+int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
+    PrefillAttnPlan plan;
+    LLMI_TRY(prefill_attn_plan(a, &plan));
     const int ld = (a.heads + 2 * a.kv_heads) * D;
     const dim3 ga((a.m + QB - 1) / QB, a.heads);
     if (a.cache_dtype == LLMI_F16) {
         hipLaunchKernelGGL(rope_kv_prefill_kernel<__half>, dim3(a.m), dim3(pf_rope_threads()), 0, s, a.qkv, a.qkv2, ld, a.p0, a.heads,
                            a.kv_heads, a.rope_tab, (__half*)a.k_cache, (__half*)a.v_cache, a.max_seq);
         if (a.mfma_planes) {
-            // split keys: chunks of cb key blocks
             const int nqb = (a.m + QM - 1) / QM;
-            int blocks = 0, max_nkb = 0;
-            for (int qb = 0; qb < nqb; ++qb) {
-                blocks += pf_nkb(qb, a.p0, a.m);
-                max_nkb = std::max(max_nkb, pf_nkb(qb, a.p0, a.m));
-            }
-            // one 8-wave workgroup per CU (128 KB of LDS): whole query blocks when they give
-            // every CU one; otherwise chunks of cb key blocks sized for ~one workgroup per CU
-            static const int n_cu = [] {
-                int dev = 0, n = 256;
-                if (hipGetDevice(&dev) == hipSuccess)
-                    (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-                return n > 0 ? n : 256;
-            }();
-            int cb = max_nkb;
-            if (a.split_ws && nqb * a.heads < n_cu) cb = std::max(1, (blocks * a.heads + n_cu - 1) / n_cu);
-            static const int cb_env = [] {  // tuning knob: key blocks per chunk (LLMI_PF_CHUNK)
-                const char* e = std::getenv("LLMI_PF_CHUNK");
-                return e ? std::atoi(e) : 0;
-            }();
-            if (a.split_ws && cb_env > 0) cb = cb_env;
-            int maxc = (max_nkb + cb - 1) / cb;
-            if (a.split_ws && (maxc > 8 || (size_t)a.heads * nqb * maxc * kPartFloats > a.split_ws_floats)) {
-                cb = max_nkb;  // no room: one chunk per query block
-                maxc = 1;
-            }
-            if (!a.split_ws) cb = max_nkb, maxc = 1;
-            int grid = 0;
-            for (int qb = 0; qb < nqb; ++qb) grid += (pf_nkb(qb, a.p0, a.m) + cb - 1) / cb;
-            // 1-D, XCD-interleaved: 8 x ceil(heads / 8) x (items per head) workgroups
-            const dim3 gm(8 * ((a.heads + 7) / 8) * grid);
+            const int cb = plan.cb, maxc = plan.maxc;
+            const dim3 gm(plan.grid);
             unsigned long long* st = g_pf_stamps.load(std::memory_order_relaxed);
 #define PF_ATTN(PL)                                                                                            \
     hipLaunchKernelGGL(attn_prefill_tr_kernel<PL>, gm, dim3(kTrThreads), 0, s, a.qkv, ld, a.m, a.p0, a.heads,  \
@@ -750,9 +787,9 @@ int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
 #define PF_MERGE(C)                                                                                              \
     hipLaunchKernelGGL(attn_prefill_merge_kernel<C>, dim3(nqb, a.heads), dim3(kThreads), 0, s, a.split_ws, maxc, cb, \
                        a.m, a.p0, a.out, a.out_hi, a.out_lo, a.heads * D, a.out_lo8)
-                if (maxc <= 2)
+                if (plan.merge_slots == 2)
                     PF_MERGE(2);
-                else if (maxc <= 4)
+                else if (plan.merge_slots == 4)
                     PF_MERGE(4);
                 else
                     PF_MERGE(8);
@@ -763,14 +800,12 @@ int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
                                a.kv_heads, (const __half*)a.k_cache, (const __half*)a.v_cache, a.max_seq, a.out,
                                a.heads * D);
         }
-    } else if (a.cache_dtype == LLMI_F32) {
+    } else {
         hipLaunchKernelGGL(rope_kv_prefill_kernel<float>, dim3(a.m), dim3(pf_rope_threads()), 0, s, a.qkv, a.qkv2, ld, a.p0, a.heads,
                            a.kv_heads, a.rope_tab, (float*)a.k_cache, (float*)a.v_cache, a.max_seq);
         hipLaunchKernelGGL(attn_prefill_kernel<float>, ga, dim3(kThreads), 0, s, a.qkv, ld, a.m, a.p0, a.heads,
                            a.kv_heads, (const float*)a.k_cache, (const float*)a.v_cache, a.max_seq, a.out,
                            a.heads * D);
-    } else {
-        LLMI_REQUIRE(false, "prefill attention: cache dtype must be f16 or f32");
     }
     LLMI_HIP(hipGetLastError());
     return LLMI_OK;

@@ -66,6 +66,16 @@ class DebugAttnOprojArgs(C.Structure):
                 ("err", C.c_void_p)]
 
 
+class DebugPrefillAttnArgs(C.Structure):
+    """llmi_debug_prefill_attn_args (include/llmi.h), field for field."""
+    _fields_ = [("qkv", C.c_void_p), ("qkv2", C.c_void_p), ("k_cache", C.c_void_p), ("v_cache", C.c_void_p),
+                ("cache_dtype", C.c_int), ("max_seq", C.c_int), ("m", C.c_int), ("p0", C.c_int),
+                ("heads", C.c_int), ("kv_heads", C.c_int), ("head_dim", C.c_int),
+                ("rope_tab", C.c_void_p), ("out", C.c_void_p), ("mfma_planes", C.c_int),
+                ("out_hi", C.c_void_p), ("out_lo", C.c_void_p), ("out_lo8", C.c_int),
+                ("split_ws", C.c_void_p), ("split_ws_floats", C.c_size_t), ("chunk_blocks", C.c_int)]
+
+
 _P, _I, _U64, _U32, _F, _SZ = C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_size_t
 _SIGS = {
     "llmi_last_error": (C.c_char_p, []),
@@ -107,6 +117,11 @@ _SIGS = {
     "llmi_debug_gemv_plan": (_I, [C.POINTER(DebugGemvArgs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "llmi_debug_attn_oproj": (_I, [C.POINTER(DebugAttnOprojArgs), _P]),
     "llmi_debug_prefill_stamps": (_I, [_P]),
+    "llmi_debug_prefill_attn": (_I, [C.POINTER(DebugPrefillAttnArgs), _P]),
+    "llmi_debug_prefill_attn_plan": (_I, [C.POINTER(DebugPrefillAttnArgs), C.POINTER(_I), C.POINTER(_I),
+                                          C.POINTER(_I), C.POINTER(_I)]),
+    "llmi_debug_rows_split": (_I, [_P, _I, _I, _I, _P, _I, _F, _P, _P, _I, _P, _I, _I, _P]),
+    "llmi_debug_w8_prepare": (_I, [_P, _I, _I, _P, C.POINTER(_I), _P]),
     "llmi_hbm_read_bench": (_I, [_SZ, _I, _P, _P, _P]),
     "llmi_batched_matmul": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "llmi_transpose_remove_pad": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),

@@ -463,6 +463,42 @@ def debug_attn_oproj(**fields) -> None:
     call("llmi_debug_attn_oproj", ctypes.byref(a), _stream())
 
 
+def debug_prefill_attn(**fields) -> None:
+    """llmi_debug_prefill_attn (test hook): one launch of the prefill attention (rope + cache
+    write, attention, merge) with llmi_debug_prefill_attn_args filled from the keywords
+    (tensors become their device addresses; the rest stays zero)."""
+    a = _debug_args(_lib.DebugPrefillAttnArgs, fields)
+    call("llmi_debug_prefill_attn", ctypes.byref(a), _stream())
+
+
+def debug_prefill_attn_plan(**fields):
+    """llmi_debug_prefill_attn_plan (test hook): (cb, maxc, grid, merge_slots) that
+    debug_prefill_attn would run for the same keywords; launches nothing."""
+    a = _debug_args(_lib.DebugPrefillAttnArgs, fields)
+    out = [ctypes.c_int(0) for _ in range(4)]
+    call("llmi_debug_prefill_attn_plan", ctypes.byref(a), *[ctypes.byref(o) for o in out])
+    return tuple(o.value for o in out)
+
+
+def debug_rows_split(x, m: int, k: int, hi=None, lo=None, ldx: int = 0, ldh: int = 0, gamma=None,
+                     eps: float = 1e-5, slab=None, ksplit: int = 0, lo8: bool = False) -> None:
+    """llmi_debug_rows_split (test hook): rows_split_launch on device tensors (ldx / ldh 0: k)."""
+    _dev(x, hi, lo, gamma, slab)
+    call("llmi_debug_rows_split", _p(x), int(ldx or k), int(m), int(k), _p(gamma),
+         _dt(gamma) if gamma is not None else F16, float(eps), _p(hi), _p(lo), int(ldh or k), _p(slab),
+         int(ksplit), int(bool(lo8)), _stream())
+
+
+def debug_w8_prepare(w16, w8, rows: int = None, cols: int = None) -> int:
+    """llmi_debug_w8_prepare (test hook): the e4m3 copy of the fp16 weight w16 [rows, cols] into
+    w8 (rows of 2 cols bytes); returns the exponent. Synchronises the stream."""
+    _dev(w16, w8)
+    e = ctypes.c_int(0)
+    call("llmi_debug_w8_prepare", _p(w16), int(w16.shape[0] if rows is None else rows),
+         int(w16.shape[1] if cols is None else cols), _p(w8), ctypes.byref(e), _stream())
+    return e.value
+
+
 def stream_errors() -> int:
     """llmi_stream_errors: read and clear the device error bits recorded on the current stream
     by the layer-API GEMM calls (16: a stream-K partial never arrived; synchronises)."""

@@ -80,6 +80,77 @@ def test_errors_are_codes_with_messages():
     assert rc == -1 and b"divide by tp_world" in L.llmi_last_error()
 
 
+PF_ROWS = [(0, 1), (0, 63), (0, 64), (0, 65), (0, 200), (20, 64), (31, 33), (33, 64), (500, 40)]
+PF_PART = 64 * 128 + 2 * 64  # fp32 elements of one chunk's partial: O rows, then m, then l
+
+
+def _pf_plan(**kw):
+    F = 0x1000  # never dereferenced
+    a = _lib.DebugPrefillAttnArgs()
+    base = dict(qkv=F, k_cache=F, v_cache=F, rope_tab=F, out=F, cache_dtype=_lib.F16, max_seq=1024, mfma_planes=2)
+    for key, v in dict(base, **kw).items():
+        setattr(a, key, v)
+    o = [C.c_int() for _ in range(4)]
+    call("llmi_debug_prefill_attn_plan", C.byref(a), *[C.byref(x) for x in o])
+    return tuple(x.value for x in o)
+
+
+def _pf_model(p0, m, heads, ws_floats, chunk_blocks, n_cu=256):
+    """The documented ladder (kernels.h PrefillAttnPlan, prefill.hip's split-key comment), restated:
+    query blocks of 64 rows, block qb sees ceil((p0 + min(64 qb + 64, m)) / 64) key blocks."""
+    nqb = -(-m // 64)
+    nkb = [-(-(p0 + min(64 * q + 64, m)) // 64) for q in range(nqb)]
+    cb = max(nkb)
+    if ws_floats is not None:
+        if nqb * heads < n_cu:
+            cb = max(1, -(-sum(nkb) * heads // n_cu))
+        if chunk_blocks:
+            cb = chunk_blocks
+    maxc = -(-max(nkb) // cb)
+    if ws_floats is None or maxc > 8 or heads * nqb * maxc * PF_PART > ws_floats:
+        cb, maxc = max(nkb), 1
+    items = sum(-(-n // cb) for n in nkb)
+    return cb, maxc, 8 * (-(-heads // 8)) * items, {1: 0, 2: 2, 3: 4, 4: 4}.get(maxc, 8)
+
+
+def test_debug_prefill_attn_plan_walks_the_ladder():
+    """llmi_debug_prefill_attn_plan launches nothing; without a GPU the CU count falls back to
+    256. Every (p0, m) of the GPU file's MFMA list at heads 4, 12 and 8: no workspace, the
+    automatic chunking and chunk_blocks 1, against the ladder restated above; then the forms
+    by hand, the workspace-size fallback and the argument checks."""
+    big = 1 << 30
+    for heads, kvh in ((4, 4), (12, 4), (8, 2)):
+        for p0, m in PF_ROWS:
+            kw = dict(p0=p0, m=m, heads=heads, kv_heads=kvh)
+            assert _pf_plan(**kw) == _pf_model(p0, m, heads, None, 0), kw
+            assert _pf_plan(split_ws=0x1000, split_ws_floats=big, **kw) == _pf_model(p0, m, heads, big, 0), kw
+            assert _pf_plan(split_ws=0x1000, split_ws_floats=big, chunk_blocks=1, **kw) == \
+                _pf_model(p0, m, heads, big, 1), kw
+            assert _pf_plan(chunk_blocks=1, **kw) == _pf_model(p0, m, heads, None, 0), kw  # no workspace: ignored
+    ws = dict(split_ws=0x1000, split_ws_floats=big)
+    assert _pf_plan(p0=0, m=1, heads=4, kv_heads=4, **ws) == (1, 1, 8, 0)
+    assert _pf_plan(p0=0, m=200, heads=12, kv_heads=4, chunk_blocks=1, **ws) == (1, 4, 160, 4)   # 1+2+3+4 items
+    assert _pf_plan(p0=33, m=64, heads=4, kv_heads=4, chunk_blocks=1, **ws) == (1, 2, 16, 2)
+    assert _pf_plan(p0=128, m=64, heads=4, kv_heads=4, chunk_blocks=1, **ws) == (1, 3, 24, 4)
+    assert _pf_plan(p0=448, m=64, heads=4, kv_heads=4, chunk_blocks=1, **ws) == (1, 8, 64, 8)
+    assert _pf_plan(p0=500, m=40, heads=8, kv_heads=2, chunk_blocks=1, **ws) == (9, 1, 8, 0)     # 9 chunks: one
+    assert _pf_plan(p0=500, m=40, heads=8, kv_heads=2, chunk_blocks=2, **ws) == (2, 5, 40, 8)
+    assert _pf_plan(p0=500, m=40, heads=12, kv_heads=4, **ws) == (9, 1, 16, 0)   # automatic cb 1 -> 9 chunks: one
+    need = 4 * 1 * 2 * PF_PART
+    kw = dict(p0=64, m=64, heads=4, kv_heads=4, split_ws=0x1000, chunk_blocks=1)
+    assert _pf_plan(split_ws_floats=need, **kw) == (1, 2, 16, 2)
+    assert _pf_plan(split_ws_floats=need - 1, **kw) == (2, 1, 8, 0)
+    assert _pf_plan(p0=20, m=64, heads=12, kv_heads=4, mfma_planes=0) == (0, 1, 24, 0)           # scalar: 32-row blocks
+    ok = dict(p0=0, m=8, heads=4, kv_heads=4)
+    for bad in (dict(heads=5), dict(heads=0), dict(kv_heads=0), dict(p0=1020), dict(m=0), dict(p0=-1),
+                dict(head_dim=64), dict(qkv=0), dict(rope_tab=0), dict(cache_dtype=_lib.F32),
+                dict(cache_dtype=_lib.I8, mfma_planes=0), dict(mfma_planes=3), dict(out=0), dict(out=0, mfma_planes=0),
+                dict(chunk_blocks=-1)):
+        with pytest.raises(_lib.LlmiError):
+            _pf_plan(**dict(ok, **bad))
+    assert _pf_plan(out=0, out_hi=0x1000, **ok) == (1, 1, 8, 0)
+
+
 def test_debug_gemv_plan_reports_the_launchers_choices():
     """llmi_debug_gemv_plan launches nothing, so its ladder is checked without a GPU: the
     x-staging width at each threshold (k / 4 float4s against 4, 5, 11, 14 x 256), the unroll
