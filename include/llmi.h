@@ -392,6 +392,30 @@ int llmi_sample_nucleus(const float* logits, int rows, int vocab, const int32_t*
                         float temperature, int top_k, float top_p, uint64_t step, int32_t* out_id /* [rows] */,
                         int32_t* out_kept /* [rows], nullable */, llmi_stream_t stream);
 
+/* Log-probabilities over whole rows of logits [rows, vocab] (f32, not modified). No reference
+ * counterpart; the rule is specified in DESIGN.md ("Log-probabilities") and restated in
+ * tests/logprob_ref.py. z is the RAW logit: no penalty and no temperature are applied, so the
+ * result describes the model's distribution, not the one a sampler draws from.
+ *   NaN counts as -inf; m = max z;
+ *   integer weights w_i = rint((double)expf(z_i - m) * 2^32); an id whose value equals the
+ *   maximum has w_i = 2^32 exactly and z_i - m := 0 (llmi_sample_nucleus's convention);
+ *   S = sum w_i, an integer sum: exact, hence the same bits in any summation order;
+ *   logprob_i = (float)(((double)z_i - (double)m) - log((double)S * 2^-32)), in double;
+ *   logsumexp = (float)((double)m + log((double)S * 2^-32)).
+ * If the maximum is +inf, the +inf entries get -log(their count) and every other id -inf; a row
+ * of only -inf / NaN gets -log(vocab) everywhere.
+ * out_lp[row] = the logprob of ids[row] (ids NULL: out_lp is not written). top_ids / top_lp
+ * [rows, n_top] = the first n_top ids of llmi_argmax's order (value descending, ties to the
+ * lower id) and their logprobs, n_top in 0..8; n_top > vocab pads with id -1 and logprob -inf.
+ * out_lse (nullable) receives the row's logsumexp. rows <= 65536, vocab <= 131072
+ * (LLMI_EUNSUPPORTED above). LLMI_EINVAL: null logits, ids without out_lp, n_top outside [0, 8]
+ * or without top_ids / top_lp, an id outside [0, vocab) (ids are read back and checked unless the
+ * stream is being captured; the kernel writes nothing for such an id). One launch, one
+ * workgroup per row; graph-capturable; allocates nothing. */
+int llmi_logprobs(const float* logits, int rows, int vocab, const int32_t* ids /* [rows], nullable */, int n_top,
+                  float* out_lp /* [rows] */, int32_t* top_ids /* [rows, n_top] */, float* top_lp /* [rows, n_top] */,
+                  float* out_lse /* [rows], nullable */, llmi_stream_t stream);
+
 /* The draw llmi_sampling makes, computed on the host (no device work): the first
  * curand_uniform of curand_init(seed, subsequence, 0) -- cuRAND's XORWOW as restated in
  * csrc/xorwow.h (subsequence < 65536). For checking the restatement against a CPU oracle. */
@@ -635,6 +659,25 @@ typedef struct llmi_sampling_params {
     uint64_t seed;
 } llmi_sampling_params;
 int llmi_engine_set_sampling_params(llmi_engine* e, const llmi_sampling_params* p);
+/* llmi_logprobs inside the token step: one more launch after the lm_head and after the sampler
+ * (and after a prefill's last row), in the eager and the captured step alike. n_top = -1: off
+ * (the default; nothing is launched and the captured step is unchanged); 0: the chosen token's
+ * logprob only; 1..8: also that many alternatives. The forward at position p writes record
+ * p + 1: the logprob, under the RAW logits of that forward (llmi_logprobs' rule: no penalty,
+ * no temperature, whatever sampler is set), of the token the sequence holds at p + 1 -- the
+ * prompt's while inside the prompt, else the id the sampler (or the argmax) chose -- and the
+ * top n_top ids of that row with their logprobs. Independent of the sampler and kept across
+ * changes of it. llmi_engine_set_prompt marks every record "not computed" (logprob NaN, ids
+ * -1); record 0 is never computed, and the prompt rows that ran through llmi_engine_prefill's
+ * batched pass stay not computed: only that call's last row forms logits, and it is recorded
+ * (scoring a text therefore steps it with llmi_engine_decode). Changing n_top discards the
+ * records. Needs tp_world == 1 and no group rank (LLMI_EUNSUPPORTED: only a vocab shard of
+ * the logits is present); vocab <= 131072. */
+int llmi_engine_set_logprobs(llmi_engine* e, int n_top);
+/* The first n records (tok_lp [n], top_ids / top_lp [n, n_top]; each nullable). *n_valid = the
+ * records that exist (positions stepped + 1, record 0 included), *n_top = the setting. Syncs. */
+int llmi_engine_logprobs(llmi_engine* e, float* tok_lp, int32_t* top_ids, float* top_lp, int n, int* n_valid,
+                         int* n_top);
 /* Reset the sequence and stage a prompt (device copy). */
 int llmi_engine_set_prompt(llmi_engine* e, const int32_t* ids, int n);
 /* Run n forward steps (one token each). use_graph: replay the captured hipGraph. */
@@ -800,9 +843,16 @@ int llmi_batch_reset(llmi_batch* b, int seq);
 /* llmi_engine_set_sampling_params for one slot: step = seed + the sampled token's position,
  * row 0, as in the engine. */
 int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_params* p);
+/* llmi_engine_set_logprobs / llmi_engine_logprobs for one slot: the setting and the records are
+ * the slot's own (one launch per active slot with logprobs on, after that slot's sampler), and
+ * bitwise those of an engine running the sequence alone. llmi_batch_set_prompt clears only
+ * that slot's records. */
+int llmi_batch_set_logprobs(llmi_batch* b, int seq, int n_top);
+int llmi_batch_logprobs(llmi_batch* b, int seq, float* tok_lp, int32_t* top_ids, float* top_lp, int n, int* n_valid,
+                        int* n_top);
 /* Every active slot advances n_steps tokens. LLMI_EINVAL if no slot is active or any active
  * slot would pass max_seq. use_graph: the step is captured per (active slots, their attention
- * split counts) in a bounded cache and replayed; replay is bitwise the eager step. */
+ * split counts and logprob settings) in a bounded cache and replayed; replay is bitwise the eager step. */
 int llmi_batch_decode(llmi_batch* b, int n_steps, int use_graph);
 int llmi_batch_tokens(llmi_batch* b, int seq, int32_t* out, int n, int* n_valid);
 int llmi_batch_logits(llmi_batch* b, int seq, float* out, int n);

@@ -25,6 +25,32 @@ namespace llm {
 // basemodel.h CallBack: index 0 = first generated token, -1 = end of the answer
 using TokenCallBack = std::function<void(int index, int token)>;
 
+// Log-probabilities of generated tokens (llmi_engine_set_logprobs): token[i] is the logprob of
+// the i-th generated token under the raw logits it was chosen from; top_ids / top_logprobs
+// [i * n_top + j] the j-th most likely id at that step and its logprob.
+struct TokenLogprobs {
+    int n_top = 0;
+    std::vector<float> token;
+    std::vector<int> top_ids;
+    std::vector<float> top_logprobs;
+};
+
+// records [first, first + count) of the engine (the generated tokens of a Response)
+inline TokenLogprobs ReadLogprobs(llmi_engine* eng, int first, int count) {
+    TokenLogprobs r;
+    int valid = 0;
+    LLMI_CALL(llmi_engine_logprobs(eng, nullptr, nullptr, nullptr, 0, &valid, &r.n_top));
+    const int n = std::min(valid, first + count);
+    if (n <= first) return r;
+    std::vector<float> lp(n), tlp((size_t)n * r.n_top);
+    std::vector<int> ids((size_t)n * r.n_top);
+    LLMI_CALL(llmi_engine_logprobs(eng, lp.data(), ids.data(), tlp.data(), n, &valid, &r.n_top));
+    r.token.assign(lp.begin() + first, lp.end());
+    r.top_ids.assign(ids.begin() + (size_t)first * r.n_top, ids.end());
+    r.top_logprobs.assign(tlp.begin() + (size_t)first * r.n_top, tlp.end());
+    return r;
+}
+
 class LlamaModel {
 public:
     // preset: "llama2-7b", "llama2-13b", "tiny"; weight_dtype LLMI_F16 / LLMI_F32 / LLMI_I8
@@ -56,6 +82,10 @@ public:
         const llmi_sampling_params p{top_k, top_p, temperature, repetition_penalty, seed};
         LLMI_CALL(llmi_engine_set_sampling_params(eng, &p));
     }
+    // per-token log-probabilities of what Response generates (llmi_engine_set_logprobs): -1 off
+    // (default), 0 the generated token's, 1..8 also that many alternatives; lastLogprobs reads them
+    void setLogprobs(int n_top) { LLMI_CALL(llmi_engine_set_logprobs(eng, n_top)); }
+    TokenLogprobs lastLogprobs() { return ReadLogprobs(eng, last_prompt, last_generated); }
 
     // Greedy generation (the reference's K = 1 top-k + sampling). tokens_per_sync
     // forwards run back to back (graph replays) between host reads, so the host
@@ -66,6 +96,8 @@ public:
         LLMI_CALL(llmi_engine_set_prompt(eng, prompt.data(), (int)prompt.size()));
         std::vector<int> out;
         std::vector<int> all(cfg.max_seq + 1);
+        last_prompt = (int)prompt.size();
+        last_generated = 0;
         int done = 0, emitted = 0;
         const int total = std::min<int>((int)prompt.size() - 1 + output_token_limit, cfg.max_seq);
         while (done < total) {
@@ -76,6 +108,7 @@ public:
             LLMI_CALL(llmi_engine_tokens(eng, all.data(), (int)all.size(), &valid));
             for (int p = (int)prompt.size() + emitted; p < valid && emitted < output_token_limit; ++p, ++emitted) {
                 out.push_back(all[p]);
+                last_generated = emitted + 1;
                 if (cb) cb(emitted, all[p]);
                 if (all[p] == eos_token_id) {
                     if (cb) cb(-1, -1);
@@ -96,6 +129,7 @@ public:
 private:
     llmi_config cfg{};
     llmi_engine* eng = nullptr;
+    int last_prompt = 0, last_generated = 0;  // the last Response's prompt length and generated count
 };
 
 // token-id variants of model_utils.h:63-82 (preset name instead of the template type)
@@ -210,6 +244,8 @@ public:
             ids.erase(ids.begin() + 1, ids.end() - (keep - 1));
         }
         LLMI_CALL(llmi_engine_set_prompt(eng, ids.data(), (int)ids.size()));
+        last_prompt = (int)ids.size();
+        last_generated = 0;
         LLMI_CALL(llmi_engine_prefill(eng, (int)ids.size(), 1));  // firstTokenGen
         std::string res;
         std::vector<int> all(cfg.max_seq + 1);
@@ -227,6 +263,7 @@ public:
                 const std::string piece = tokenizer.Decode({tok});
                 res += piece;
                 if (PrintRes) PrintRes(produced, piece.c_str());
+                last_generated = produced + 1;
                 if (++produced >= limit) done = true;
             }
             if (done) break;
@@ -245,6 +282,12 @@ public:
         const llmi_sampling_params p{top_k, top_p, temperature, repetition_penalty, seed};
         LLMI_CALL(llmi_engine_set_sampling_params(eng, &p));
     }
+
+    // per-token log-probabilities of the pieces Response generates (llmi_engine_set_logprobs: -1
+    // off, 0 the token's own, 1..8 also that many alternatives), read by lastLogprobs. The
+    // prompt itself is prefilled in one batched pass and is not scored.
+    void setLogprobs(int n_top) { LLMI_CALL(llmi_engine_set_logprobs(eng, n_top)); }
+    llm::TokenLogprobs lastLogprobs() { return llm::ReadLogprobs(eng, last_prompt, last_generated); }
 
     // the generated ids of the last Response (for tests and callers that keep ids)
     std::vector<int> lastTokens() {
@@ -267,6 +310,7 @@ private:
     float rmsnorm_eps = 1e-5f;  // llama.h:22
     llmi_config cfg{};
     llmi_engine* eng = nullptr;
+    int last_prompt = 0, last_generated = 0;
     Tokenizer tokenizer;
 };
 

@@ -428,6 +428,11 @@ int llmi_sample_nucleus(const float* logits, int rows, int vocab, const int32_t*
                                  temperature, top_k, top_p, step, out_id, out_kept, STREAM(stream));
 }
 
+int llmi_logprobs(const float* logits, int rows, int vocab, const int32_t* ids, int n_top, float* out_lp,
+                  int32_t* top_ids, float* top_lp, float* out_lse, llmi_stream_t stream) {
+    return logprobs_launch(logits, rows, vocab, ids, n_top, out_lp, top_ids, top_lp, out_lse, STREAM(stream));
+}
+
 int llmi_repeat_kv(const void* k_cache, const void* v_cache, int dtype, int layer, const int32_t* context_length,
                    int batch, int kv_heads, int max_seq, int heads, int max_k_len, int head_dim, void* k_dst,
                    void* v_dst, llmi_stream_t stream) {

@@ -242,8 +242,21 @@ struct Engine {
     llmi_sampling_params nuc{};
     int32_t* samp_ids = nullptr;
     float* samp_vals = nullptr;
+    // llmi_engine_set_logprobs: -1 off, else the alternatives per record; one blob of
+    // max_seq + 1 records each of tok_lp, top_ids [kLpMaxTop], top_lp [kLpMaxTop] (the two
+    // top arrays are indexed with stride lp_top), 0xFF-filled = "not computed"
+    static constexpr int kLpMaxTop = 8;
+    int lp_top = -1;
+    int lp_stride = -1;  // the n_top the records were laid out for (kept while off)
+    char* lp_buf = nullptr;
+    size_t lp_records() const { return (size_t)c.max_seq + 1; }
+    size_t lp_bytes() const { return lp_records() * 4 * (1 + 2 * kLpMaxTop); }
+    float* lp_tok() const { return reinterpret_cast<float*>(lp_buf); }
+    int32_t* lp_ids() const { return reinterpret_cast<int32_t*>(lp_buf + lp_records() * 4); }
+    float* lp_tlp() const { return reinterpret_cast<float*>(lp_buf + lp_records() * 4 * (1 + kLpMaxTop)); }
 
     ~Engine() {  // teardown errors are not actionable; ignore them explicitly
+        if (lp_buf) (void)hipFree(lp_buf);
         if (samp_ids) (void)hipFree(samp_ids);
         if (samp_vals) (void)hipFree(samp_vals);
         graphs.clear();
@@ -910,12 +923,23 @@ struct Engine {
     // (history tokens[0 .. cur_pos]: step_start / prefill_finish have written them), or
     // top-K of this token's logits and the reference's pick
     int rec_sample() {
+        LLMI_TRY(rec_pick());
+        return rec_logprob();
+    }
+    int rec_pick() {
         if (nuc_on)
             return engine_nucleus_launch(st, logits, c.vocab, tokens, nuc.repetition_penalty, nuc.temperature,
                                          nuc.top_k, nuc.top_p, nuc.seed, partials, lm_grid, stream);
         if (sample_k == 0) return LLMI_OK;
         LLMI_TRY(topk_launch(logits, LLMI_F32, 1, c.vocab, sample_k, samp_ids, samp_vals, stream));
         return sample_pick_launch(st, samp_ids, samp_vals, sample_k, sample_seed, partials, lm_grid, stream);
+    }
+    // record cur_pos + 1: the raw row's logprob of the token step_start will pick there (the
+    // prompt's, or the one the partials name now that the sampler has run) and the top-n
+    int rec_logprob() {
+        if (lp_top < 0) return LLMI_OK;
+        return engine_logprob_launch(st, logits, c.vocab, prompt, partials, lm_grid, c.max_seq, lp_top, lp_tok(),
+                                     lp_ids(), lp_tlp(), stream);
     }
 
     // ------------------------------------------------- TP exchange (config 4)
@@ -1030,6 +1054,43 @@ struct Engine {
         nuc = p;
         nuc_on = true;
         sample_k = 0;
+        return LLMI_OK;
+    }
+
+    // -1 off, 0 the chosen token's logprob, 1..8 also that many alternatives. Independent of
+    // the sampler (it reads the raw row and whatever id the partials name).
+    int set_logprobs(int n_top) {
+        LLMI_REQUIRE(n_top >= -1 && n_top <= kLpMaxTop, "set_logprobs: n_top must be -1 (off) or in [0, 8]");
+        if (n_top >= 0) {
+            if (c.tp_world != 1 || grouped) {
+                set_last_error("[llmi][ERROR] set_logprobs: logprobs need the full logits row (tp_world 1, no group rank)");
+                return LLMI_EUNSUPPORTED;
+            }
+            LLMI_TRY(engine_logprob_check(c.vocab, n_top));
+        }
+        LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
+        graphs.clear();                          // the captured step changes
+        if (n_top >= 0 && !lp_buf) LLMI_HIP(hipMalloc(&lp_buf, lp_bytes()));
+        if (n_top >= 0 && n_top != lp_stride) {  // the record stride changes: nothing computed so far is readable
+            LLMI_HIP(hipMemsetAsync(lp_buf, 0xFF, lp_bytes(), stream));
+            LLMI_HIP(hipStreamSynchronize(stream));
+            lp_stride = n_top;
+        }
+        lp_top = n_top;
+        return LLMI_OK;
+    }
+    // records 0 .. n_valid - 1 (n_valid = positions stepped + 1; record 0 is never computed)
+    int logprobs_out(float* tok_lp, int32_t* top_ids, float* top_lp, int n, int* n_valid, int* n_top) {
+        LLMI_REQUIRE(lp_top >= 0 && lp_buf, "logprobs: set_logprobs first");
+        LLMI_REQUIRE(n >= 0, "logprobs: n must be >= 0");
+        LLMI_HIP(hipStreamSynchronize(stream));
+        const int valid = prompt_len > 0 ? std::min(host_next_pos, c.max_seq) + 1 : 0;
+        const size_t m = (size_t)std::min(n, valid);
+        if (m > 0 && tok_lp) LLMI_HIP(hipMemcpy(tok_lp, lp_tok(), m * 4, hipMemcpyDeviceToHost));
+        if (m > 0 && lp_top > 0 && top_ids) LLMI_HIP(hipMemcpy(top_ids, lp_ids(), m * lp_top * 4, hipMemcpyDeviceToHost));
+        if (m > 0 && lp_top > 0 && top_lp) LLMI_HIP(hipMemcpy(top_lp, lp_tlp(), m * lp_top * 4, hipMemcpyDeviceToHost));
+        if (n_valid) *n_valid = valid;
+        if (n_top) *n_top = lp_top;
         return LLMI_OK;
     }
 
@@ -1152,6 +1213,7 @@ struct Engine {
         // (the epoch and what follows it are left alone: the fused q/k/v launch's granule tags
         // must never repeat the tag its buffer already holds, across prompts too)
         LLMI_HIP(hipMemcpyAsync(st, &h, offsetof(DecodeState, epoch), hipMemcpyHostToDevice, stream));
+        if (lp_buf) LLMI_HIP(hipMemsetAsync(lp_buf, 0xFF, lp_bytes(), stream));  // NaN / id -1: not computed
         LLMI_HIP(hipStreamSynchronize(stream));
         host_next_pos = 0;
         prompt_len = n;
@@ -1596,7 +1658,7 @@ struct Group {
 struct Batch {
     std::vector<std::unique_ptr<Engine>> r;
     hipStream_t stream = nullptr;
-    // captured steps by key {slot, nact, slot, nact, ...} of the active slots; bounded: a full
+    // captured steps by key {slot, nact, logprobs, ...} of the active slots; bounded: a full
     // cache is dropped whole (after a sync) before the next capture
     static constexpr size_t kMaxGraphs = 64;
     std::map<std::vector<int>, std::pair<hipGraph_t, hipGraphExec_t>> graphs;
@@ -1713,6 +1775,7 @@ struct Batch {
                 r[s]->rec_nact = Engine::nact_of(r[s]->host_next_pos + i);
                 key.push_back(s);
                 key.push_back(r[s]->rec_nact);
+                key.push_back(r[s]->lp_top);  // the slot's logprob launch (or none) is part of the step
             }
             if (!use_graph) {
                 LLMI_TRY(record_step(act));
@@ -1896,6 +1959,19 @@ int llmi_engine_load_bin(llmi_engine* e, const char* weight_path) {
     LLMI_REQUIRE(e, "null engine");
     LLMI_HIP(hipSetDevice(e->e.device));
     return e->e.load_bin(weight_path);
+}
+
+int llmi_engine_set_logprobs(llmi_engine* e, int n_top) {
+    LLMI_REQUIRE(e, "engine_set_logprobs: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.set_logprobs(n_top);
+}
+
+int llmi_engine_logprobs(llmi_engine* e, float* tok_lp, int32_t* top_ids, float* top_lp, int n, int* n_valid,
+                         int* n_top) {
+    LLMI_REQUIRE(e, "engine_logprobs: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.logprobs_out(tok_lp, top_ids, top_lp, n, n_valid, n_top);
 }
 
 int llmi_engine_set_prompt(llmi_engine* e, const int32_t* ids, int n) {
@@ -2379,6 +2455,21 @@ int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_p
     LLMI_HIP(hipSetDevice(b->b.r[0]->device));
     LLMI_TRY(b->b.r[seq]->set_sampling_params(*p));
     return b->b.drop_graphs();  // the captured steps change
+}
+
+int llmi_batch_set_logprobs(llmi_batch* b, int seq, int n_top) {
+    LLMI_REQUIRE(b, "batch_set_logprobs: null batch");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    return b->b.r[seq]->set_logprobs(n_top);  // (the graph key carries every slot's setting)
+}
+
+int llmi_batch_logprobs(llmi_batch* b, int seq, float* tok_lp, int32_t* top_ids, float* top_lp, int n, int* n_valid,
+                        int* n_top) {
+    LLMI_REQUIRE(b, "batch_logprobs: null batch");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    return b->b.r[seq]->logprobs_out(tok_lp, top_ids, top_lp, n, n_valid, n_top);
 }
 
 int llmi_batch_decode(llmi_batch* b, int n_steps, int use_graph) {

@@ -524,6 +524,17 @@ int engine_nucleus_check(int vocab, float penalty, float temperature, int top_k,
 int engine_nucleus_launch(const struct DecodeState* st, const float* logits, int vocab, const int32_t* tokens,
                           float penalty, float temperature, int top_k, float top_p, uint64_t seed,
                           unsigned long long* partials, int np, hipStream_t s);
+// log-probabilities of whole rows of raw logits (logprob.hip): the scored id's (ids, nullable),
+// the first n_top of the argmax_key order, the row's logsumexp (nullable)
+int logprobs_launch(const float* logits, int rows, int vocab, const int32_t* ids, int n_top, float* out_lp,
+                    int32_t* top_ids, float* top_lp, float* out_lse, hipStream_t s);
+// engine form: record q = cur_pos + 1 of tok_lp / top_ids / top_lp (max_seq + 1 records), the
+// scored id the one step_start will pick for q: prompt[q], or the argmax of the partials as
+// the sampler left them. Reads only; runs after the sampler.
+int engine_logprob_check(int vocab, int n_top);
+int engine_logprob_launch(const struct DecodeState* st, const float* logits, int vocab, const int32_t* prompt,
+                          const unsigned long long* partials, int np, int max_seq, int n_top, float* tok_lp,
+                          int32_t* top_ids, float* top_lp, hipStream_t s);
 int repeat_kv_launch(const void* k_cache, const void* v_cache, int dtype, int layer, const int* ctx_len, int batch,
                      int kv_heads, int max_seq, int heads, int max_k_len, int d, void* k_dst, void* v_dst,
                      hipStream_t s);

@@ -23,17 +23,17 @@
 #include <vector>
 
 #include "kernels.h"
+#include "rowkeys.h"
 #include "xorwow.h"
 
 namespace llmi {
 namespace {
 
-constexpr int kNucThreads = 1024;
+constexpr int kNucThreads = kRowThreads;
 constexpr int kNucWaves = kNucThreads / kWave;
 constexpr int kNucBuckets = 2 * kNucThreads;
 constexpr int kNucLdsVocab = 32768;      // keys held in LDS up to here
 constexpr int kNucMaxVocab = 131072;     // bitmap 16 KB
-constexpr unsigned long long kOne = 1ull << 32;
 
 struct NucArgs {
     const float* logits;
@@ -62,15 +62,6 @@ __device__ __forceinline__ bool in_cut(uint32_t key, int i, Cut c) {
     return key > c.tau || (key == c.tau && i <= c.idc);
 }
 
-__device__ __forceinline__ uint32_t key_of(float z) { return (uint32_t)(argmax_key(z, 0u) >> 32); }
-__device__ __forceinline__ float z_of(uint32_t key) {
-    return __uint_as_float((key & 0x80000000u) ? (key ^ 0x80000000u) : ~key);
-}
-__device__ __forceinline__ unsigned long long weight_of(uint32_t key, uint32_t mkey, float m) {
-    if (key == mkey) return kOne;  // also +inf and all -inf rows, where z - m is NaN
-    return (unsigned long long)rint((double)expf(z_of(key) - m) * 4294967296.0);
-}
-
 // scratch at the head of the dynamic LDS region
 struct NucScratch {
     unsigned long long red[kNucWaves];
@@ -80,30 +71,6 @@ struct NucScratch {
     float u;
     int pad[3];
 };
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_scan_u64(unsigned long long v, int lane) {
-#pragma unroll
-    for (int off = 1; off < kWave; off <<= 1) {
-        const unsigned long long t = __shfl_up(v, off, kWave);
-        if (lane >= off) v += t;
-    }
-    return v;
-}
-__device__ unsigned long long block_sum_u64(unsigned long long v, NucScratch* sc) {
-    v = wave_sum_u64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sc->red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    unsigned long long t = 0;
-#pragma unroll
-    for (int i = 0; i < kNucWaves; ++i) t += sc->red[i];
-    return t;
-}
 
 template <bool kLds>
 struct Row {
@@ -134,8 +101,8 @@ __device__ void cut_totals(const Row<kLds>& r, Cut c, uint32_t mkey, float m, Nu
             n += 1;
         }
     }
-    *sum = block_sum_u64(s, sc);
-    *count = (int)block_sum_u64(n, sc);
+    *sum = block_sum_u64(s, sc->red);
+    *count = (int)block_sum_u64(n, sc->red);
 }
 
 // smallest id whose id-order running sum of q(i) reaches target (>= 1, <= the total)

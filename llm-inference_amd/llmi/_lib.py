@@ -96,6 +96,7 @@ _SIGS = {
     "llmi_topk": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "llmi_sampling": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     "llmi_sample_nucleus": (_I, [_P, _I, _I, _P, _I, _P, _F, _F, _I, _F, _U64, _P, _P, _P]),
+    "llmi_logprobs": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
     "llmi_repeat_kv": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "llmi_padding_offset": (_I, [_P, _P, _P, _I, _I, _P]),
     "llmi_rope_qkv_prefill": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
@@ -146,6 +147,8 @@ _SIGS = {
     "llmi_engine_load_bin": (_I, [_P, C.c_char_p]),
     "llmi_engine_set_sampling": (_I, [_P, _I, _U64]),
     "llmi_engine_set_sampling_params": (_I, [_P, _P]),
+    "llmi_engine_set_logprobs": (_I, [_P, _I]),
+    "llmi_engine_logprobs": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I), C.POINTER(_I)]),
     "llmi_engine_load_tensor": (_I, [_P, C.c_char_p, _P, _SZ]),
     "llmi_engine_load_bin_quantized": (_I, [_P, C.c_char_p]),
     "llmi_engine_load_tensor_quantized": (_I, [_P, C.c_char_p, _P, _SZ]),
@@ -189,6 +192,8 @@ _SIGS = {
     "llmi_batch_set_prompt": (_I, [_P, _I, _P, _I]),
     "llmi_batch_reset": (_I, [_P, _I]),
     "llmi_batch_set_sampling_params": (_I, [_P, _I, _P]),
+    "llmi_batch_set_logprobs": (_I, [_P, _I, _I]),
+    "llmi_batch_logprobs": (_I, [_P, _I, _P, _P, _P, _I, C.POINTER(_I), C.POINTER(_I)]),
     "llmi_batch_decode": (_I, [_P, _I, _I]),
     "llmi_batch_tokens": (_I, [_P, _I, _P, _I, C.POINTER(_I)]),
     "llmi_batch_logits": (_I, [_P, _I, _P, _I]),

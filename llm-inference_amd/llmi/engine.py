@@ -36,6 +36,19 @@ def synth_prompt(seed: int, n: int, vocab: int) -> np.ndarray:
     return out
 
 
+def _read_logprobs(fn: str, handle: tuple, n: int):
+    """The records of llmi_engine_logprobs / llmi_batch_logprobs as numpy arrays."""
+    valid, top = C.c_int(), C.c_int()
+    call(fn, *handle, None, None, None, 0, C.byref(valid), C.byref(top))
+    n, k = min(n, valid.value), top.value
+    lp = np.zeros(n, np.float32)
+    ids = np.zeros((n, k), np.int32)
+    tlp = np.zeros((n, k), np.float32)
+    call(fn, *handle, lp.ctypes.data, ids.ctypes.data if k else None, tlp.ctypes.data if k else None, n,
+         C.byref(valid), C.byref(top))
+    return lp, ids, tlp
+
+
 class Engine:
     def __init__(self, cfg: Config, device: int = 0, tp_id: Optional[bytes] = None):
         self.cfg = cfg
@@ -43,6 +56,7 @@ class Engine:
         idbuf = C.create_string_buffer(tp_id, 128) if tp_id else None
         call("llmi_engine_create", C.byref(cfg), device, idbuf, C.byref(h))
         self._h = h
+        self._lp_top = -1
 
     def close(self):
         if getattr(self, "_h", None):
@@ -76,6 +90,36 @@ class Engine:
         sampler; set_sampling (any k) replaces this one."""
         p = _lib.SamplingParams(int(top_k), float(top_p), float(temperature), float(repetition_penalty), int(seed))
         call("llmi_engine_set_sampling_params", self._h, C.byref(p))
+
+    def set_logprobs(self, n_top: int):
+        """Per-token log-probabilities in the token step (llmi_engine_set_logprobs): -1 off (the
+        default), 0 the chosen token's logprob, 1..8 also that many alternatives. They are those
+        of the raw logits (no penalty, no temperature), whatever sampler is set."""
+        call("llmi_engine_set_logprobs", self._h, int(n_top))
+        self._lp_top = int(n_top)
+
+    def logprobs(self, n: Optional[int] = None):
+        """(tok_lp [n], top_ids [n, n_top], top_lp [n, n_top]) of the first n records (None: all
+        that exist). Record p holds the logprob of the sequence's token at position p under the
+        forward at p - 1; NaN / id -1 = not computed (record 0, and prompt rows a batched prefill
+        consumed)."""
+        return _read_logprobs("llmi_engine_logprobs", (self._h,), self.cfg.max_seq + 1 if n is None else int(n))
+
+    def score(self, ids, use_graph: bool = True) -> np.ndarray:
+        """Log-likelihood of a given text: logprob of ids[p] given ids[:p] for p = 1 .. len - 1
+        (fp32 [len - 1]; their negated mean is the log-perplexity). Steps the text through
+        len - 1 decode steps; turns logprobs on (n_top 0) for the call if they are off."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        was = self._lp_top
+        if was < 0:
+            self.set_logprobs(0)
+        try:
+            self.set_prompt(ids)
+            self.decode(len(ids) - 1, use_graph)
+            return self.logprobs(len(ids))[0][1:]
+        finally:
+            if was < 0:
+                self.set_logprobs(-1)
 
     def load_bin(self, weight_path: str, quantize: bool = False):
         """Llama<T>::loadWeights(weight_path): weight_path + "<name>.bin" raw fp32 files
@@ -277,6 +321,7 @@ class Batch:
         h = C.c_void_p()
         call("llmi_batch_create", C.byref(cfg), n_seq, device, C.byref(h))
         self._h = h
+        self._lp_top = [-1] * n_seq
 
     def close(self):
         if getattr(self, "_h", None):
@@ -315,6 +360,50 @@ class Batch:
                             repetition_penalty: float = 1.0, seed: int = 0):
         p = _lib.SamplingParams(int(top_k), float(top_p), float(temperature), float(repetition_penalty), int(seed))
         call("llmi_batch_set_sampling_params", self._h, int(seq), C.byref(p))
+
+    def set_logprobs(self, seq: int, n_top: int):
+        """Engine.set_logprobs for one slot (the setting and the records are the slot's own)."""
+        call("llmi_batch_set_logprobs", self._h, int(seq), int(n_top))
+        self._lp_top[int(seq)] = int(n_top)
+
+    def logprobs(self, seq: int, n: Optional[int] = None):
+        """Engine.logprobs for one slot (before the slot is reset: an idle slot has no records)."""
+        return _read_logprobs("llmi_batch_logprobs", (self._h, int(seq)),
+                              self.cfg.max_seq + 1 if n is None else int(n))
+
+    def score(self, texts, use_graph: bool = True) -> list:
+        """Engine.score over up to n_seq texts of different lengths at once: slot i steps
+        texts[i] (None: idle) and goes idle when its text ends. Returns one fp32 [len - 1]
+        array per text. Slots with logprobs off have them on (n_top 0) for the call."""
+        if len(texts) > self.n_seq:
+            raise ValueError("score: more texts than slots")
+        was = list(self._lp_top)
+        left, out = {}, [None] * len(texts)
+        try:
+            for i in range(self.n_seq):
+                self.reset(i)
+            for i, t in enumerate(texts):
+                if t is None:
+                    continue
+                t = np.ascontiguousarray(t, np.int32)
+                if was[i] < 0:
+                    self.set_logprobs(i, 0)
+                self.set_prompt(i, t)
+                left[i] = len(t) - 1
+            while left:
+                n = min(left.values())
+                self.decode(n, use_graph)
+                for i in list(left):
+                    left[i] -= n
+                    if left[i] == 0:
+                        out[i] = self.logprobs(i, len(texts[i]))[0][1:]
+                        self.reset(i)
+                        del left[i]
+        finally:
+            for i in range(len(texts)):
+                if was[i] < 0 and self._lp_top[i] >= 0:
+                    self.set_logprobs(i, -1)
+        return out
 
     def decode(self, n_steps: int, use_graph: bool = True):
         """Every active slot advances n_steps tokens."""

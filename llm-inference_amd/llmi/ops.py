@@ -174,6 +174,30 @@ def sample_nucleus(logits: torch.Tensor, step: int, top_k: int = 0, top_p: float
     return out_id, out_kept
 
 
+def logprobs(logits: torch.Tensor, ids: torch.Tensor = None, n_top: int = 0):
+    """llmi_logprobs (no reference counterpart): logits [rows, vocab] (or [vocab]) fp32, left
+    unchanged and taken raw (no penalty, no temperature); ids int32 [rows] (None: none scored).
+    Returns (lp, top_ids, top_lp, lse): lp fp32 [rows] the logprob of ids[row] (None without
+    ids), top_ids int32 / top_lp fp32 [rows, n_top] the first n_top ids by (value descending,
+    id ascending) and their logprobs (padded with -1 / -inf past the vocabulary), lse fp32
+    [rows] the row's logsumexp."""
+    _dev(logits, ids)
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("logprobs: logits must be contiguous float32")
+    x = logits.view(-1, logits.shape[-1])
+    rows, vocab = x.shape
+    if ids is not None and (ids.dtype != torch.int32 or not ids.is_contiguous() or ids.numel() != rows):
+        raise ValueError("logprobs: ids must be contiguous int32 [rows]")
+    n_top = int(n_top)
+    lp = torch.empty(rows, device=x.device, dtype=torch.float32) if ids is not None else None
+    lse = torch.empty(rows, device=x.device, dtype=torch.float32)
+    top_ids = torch.empty(rows, max(n_top, 0), device=x.device, dtype=torch.int32)
+    top_lp = torch.empty(rows, max(n_top, 0), device=x.device, dtype=torch.float32)
+    call("llmi_logprobs", x.data_ptr(), rows, vocab, _p(ids), n_top, _p(lp), top_ids.data_ptr() if n_top > 0 else None,
+         top_lp.data_ptr() if n_top > 0 else None, lse.data_ptr(), _stream())
+    return lp, top_ids, top_lp, lse
+
+
 def launchSampling(topk_id, topk_val, seqlen, is_finished, output_id, step: int, end_id: int, vocab_size: int):
     """In place, like the reference (sampling.cu:87-115, params step/end_id/vocab_size from
     its IntDict): topk_val <- exp(v - v[0]); output_id, seqlen, is_finished (uint8/bool)
