@@ -1,5 +1,5 @@
 // Internal kernel launch interface (C++). The public C ABI (include/llmi.h)
-// and the decode engine (engine.hip) are both built on these.
+// and the decode engine (engine.h, engine*.hip) are both built on these.
 #pragma once
 #include <cmath>
 

@@ -1,4 +1,4 @@
-"""Batched decode (llmi_batch_*, struct Batch in engine.hip): a sequence decoded in a batch
+"""Batched decode (llmi_batch_*, struct Batch in engine_batch.hip): a sequence decoded in a batch
 gives BITWISE the tokens and the final logits it gives alone in a plain Engine with the same
 configuration, seed and default options. No tolerance anywhere: np.array_equal on ids and on
 the logits' raw bits.
