@@ -670,7 +670,8 @@ int llmi_engine_set_sampling_params(llmi_engine* e, const llmi_sampling_params* 
  * changes of it. llmi_engine_set_prompt marks every record "not computed" (logprob NaN, ids
  * -1); record 0 is never computed, and the prompt rows that ran through llmi_engine_prefill's
  * batched pass stay not computed: only that call's last row forms logits, and it is recorded
- * (scoring a text therefore steps it with llmi_engine_decode). Changing n_top discards the
+ * (llmi_engine_prefill_scored fills them; without it, scoring a text steps it with
+ * llmi_engine_decode). Changing n_top discards the
  * records. Needs tp_world == 1 and no group rank (LLMI_EUNSUPPORTED: only a vocab shard of
  * the logits is present); vocab <= 131072. */
 int llmi_engine_set_logprobs(llmi_engine* e, int n_top);
@@ -697,6 +698,25 @@ int llmi_engine_decode(llmi_engine* e, int n_steps, int use_graph);
  * Rows must lie inside the prompt; tp_world must be 1. fp32 weights run the
  * decode kernels row by row. */
 int llmi_engine_prefill(llmi_engine* e, int n_tokens, int exact);
+/* llmi_engine_prefill that also fills the log-probability records of the rows it consumes
+ * (prompt "echo" logprobs, text scoring at prefill speed). Arguments, checks and effect are
+ * llmi_engine_prefill's: tokens, the final logits, the decode state and the KV cache are
+ * bitwise what that call leaves, and so is the record of the call's last row. In addition,
+ * after each chunk's layers, the final RMSNorm and an lm_head GEMM over the chunk's rows
+ * write fp32 logits into a slab [512][vocab] (allocated on the first scored call: 65.5 MB at
+ * vocab 32000), and one launch of the logprob kernel lets every row p but the call's last
+ * write record p + 1 with the scored id prompt[p + 1] -- llmi_logprobs' rule on the raw
+ * logits. The head GEMM runs on the path the layers took (exact 1 and 2: two fp16 activation
+ * planes -- there is no e4m3 copy of the lm_head; exact 0: one), so a record agrees with the
+ * token step's to the GEMM's accuracy, not bitwise. Where no GEMM form takes the lm_head
+ * shape (and for fp32 weights) the call runs as decode steps, which score every row.
+ * LLMI_EINVAL when logprobs are off (llmi_engine_set_logprobs first); nothing is launched on
+ * an error. */
+int llmi_engine_prefill_scored(llmi_engine* e, int n_tokens, int exact);
+/* Test / debug read-back: the first n fp32 logits of prompt position pos as the last scored
+ * chunk's lm_head GEMM left them (the call's last row included). LLMI_EINVAL if that chunk
+ * does not hold pos (llmi_engine_set_prompt forgets the chunk). Syncs. */
+int llmi_engine_scored_logits(llmi_engine* e, int pos, float* out, int n);
 /* Block until the engine stream is idle. */
 int llmi_engine_sync(llmi_engine* e);
 /* Tokens[0 .. n) of the sequence so far: prompt ids followed by generated ids
@@ -854,6 +874,14 @@ int llmi_batch_logprobs(llmi_batch* b, int seq, float* tok_lp, int32_t* top_ids,
  * slot would pass max_seq. use_graph: the step is captured per (active slots, their attention
  * split counts and logprob settings) in a bounded cache and replayed; replay is bitwise the eager step. */
 int llmi_batch_decode(llmi_batch* b, int n_steps, int use_graph);
+/* llmi_engine_prefill (scored != 0: llmi_engine_prefill_scored) of slot seq's next n_tokens
+ * prompt rows, on the batch's stream. The other slots are untouched; the slot ends where
+ * n_tokens decode steps would have left it, bitwise as an engine that prefilled alone, and
+ * the next llmi_batch_decode steps it with the others. The prefill scratch, the e4m3 weight
+ * copies of exact = 2 and the logits slab exist once per batch (slot 0 owns them, one stream
+ * serialises their use); a llmi_batch_load_* drops the e4m3 copies. LLMI_EINVAL for a seq out
+ * of range, an idle slot or rows past the slot's prompt. */
+int llmi_batch_prefill(llmi_batch* b, int seq, int n_tokens, int exact, int scored);
 int llmi_batch_tokens(llmi_batch* b, int seq, int32_t* out, int n, int* n_valid);
 int llmi_batch_logits(llmi_batch* b, int seq, float* out, int n);
 int llmi_batch_sync(llmi_batch* b);

@@ -246,7 +246,10 @@ public:
         LLMI_CALL(llmi_engine_set_prompt(eng, ids.data(), (int)ids.size()));
         last_prompt = (int)ids.size();
         last_generated = 0;
-        LLMI_CALL(llmi_engine_prefill(eng, (int)ids.size(), 1));  // firstTokenGen
+        if (score_prompt_)  // firstTokenGen, the prompt's records filled
+            LLMI_CALL(llmi_engine_prefill_scored(eng, (int)ids.size(), 1));
+        else
+            LLMI_CALL(llmi_engine_prefill(eng, (int)ids.size(), 1));  // firstTokenGen
         std::string res;
         std::vector<int> all(cfg.max_seq + 1);
         const int limit = std::min(output_token_limit, cfg.max_seq - (int)ids.size() + 1);
@@ -285,9 +288,17 @@ public:
 
     // per-token log-probabilities of the pieces Response generates (llmi_engine_set_logprobs: -1
     // off, 0 the token's own, 1..8 also that many alternatives), read by lastLogprobs. The
-    // prompt itself is prefilled in one batched pass and is not scored.
-    void setLogprobs(int n_top) { LLMI_CALL(llmi_engine_set_logprobs(eng, n_top)); }
+    // prompt itself is prefilled in one batched pass; score_prompt: that pass is the scored
+    // prefill (llmi_engine_prefill_scored), so the prompt's own records are filled too and
+    // lastPromptLogprobs reads them ("echo" logprobs). What Response generates is the same.
+    void setLogprobs(int n_top) { setLogprobs(n_top, false); }
+    void setLogprobs(int n_top, bool score_prompt) {
+        LLMI_CALL(llmi_engine_set_logprobs(eng, n_top));
+        score_prompt_ = n_top >= 0 && score_prompt;
+    }
     llm::TokenLogprobs lastLogprobs() { return llm::ReadLogprobs(eng, last_prompt, last_generated); }
+    // records 1 .. prompt length - 1: prompt token p under the forward at p - 1 (score_prompt)
+    llm::TokenLogprobs lastPromptLogprobs() { return llm::ReadLogprobs(eng, 1, last_prompt - 1); }
 
     // the generated ids of the last Response (for tests and callers that keep ids)
     std::vector<int> lastTokens() {
@@ -311,6 +322,7 @@ private:
     llmi_config cfg{};
     llmi_engine* eng = nullptr;
     int last_prompt = 0, last_generated = 0;
+    bool score_prompt_ = false;
     Tokenizer tokenizer;
 };
 

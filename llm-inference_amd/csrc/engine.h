@@ -233,6 +233,14 @@ struct Engine {
     // the SiLU output planes reuse pf_act's bytes (fp32 [R, il] = two fp16 planes)
     _Float16* pf_act_h() { return reinterpret_cast<_Float16*>(pf_act); }
     _Float16* pf_act_l() { return reinterpret_cast<_Float16*>(pf_act) + (size_t)pf_rows * il; }
+    // scored prefill: fp32 logits of one chunk's rows [pf_rows][vocab] (allocated on first use,
+    // never touched by the plain prefill), and the prompt rows [sc_p0, sc_p0 + sc_m) the last
+    // scored chunk's lm_head GEMM left there
+    float* sc_logits = nullptr;
+    int sc_p0 = 0, sc_m = 0;
+    // a batch slot borrows slot 0's prefill scratch, e4m3 weight copies and logits slab (the
+    // pointers above are copies taken at every prefill; nothing of them is freed by the slot)
+    Engine* pf_from = nullptr;
 
     // --------------------------------------------------------------- ring
     // decode mode 1: the persistent ring layer (ring.hip) -- per token step_start, q/k/v(0),
@@ -364,7 +372,12 @@ struct Engine {
     PrefillAttnArgs prefill_attn_args(int l, int m, int p0) const;
     int prefill_layer_gemm2(int l, int m, int p0, int split);
     int prefill_flush(int m);
-    int prefill(int n, int split);
+    int alloc_score();
+    int prefill_scratch(int split, bool scored);
+    bool head_gemm_supported(bool use_gemm2) const;
+    int score_chunk(int m, int p0, int split, bool use_gemm2, bool last);
+    int prefill(int n, int split, bool scored = false);
+    int scored_logits_out(int pos, float* out, int n);
 };
 
 // In-process tensor-parallel group: W rank engines (tp_rank 0..W-1) on ONE
@@ -400,7 +413,9 @@ struct Group {
 // split count), ONE multi-row GEMV for gate_up and ONE for down, then ONE for the lm_head and
 // each slot's sampler. The multi-row GEMV gives every row bitwise the single-row result, and
 // everything else is the engine's own launch, so a slot's tokens and logits are bitwise those
-// of an Engine decoding the sequence alone. W_o is still streamed once per slot.
+// of an Engine decoding the sequence alone. W_o is still streamed once per slot. A slot's prompt
+// can run through the engine's own (scored) prefill, one slot per call, on slot 0's prefill
+// scratch, e4m3 weight copies and logits slab (Engine::pf_from): once per batch, not per slot.
 struct Batch {
     std::vector<std::unique_ptr<Engine>> r;
     hipStream_t stream = nullptr;
@@ -421,6 +436,7 @@ struct Batch {
     int rows(const std::vector<int>& act, F&& args_of);  // engine_batch.hip, its only user
     int record_step(const std::vector<int>& act);
     int decode(int n, int use_graph);
+    int prefill(int seq, int n, int split, bool scored);
 };
 
 }  // namespace llmi

@@ -496,6 +496,7 @@ int Engine::set_prompt(const int32_t* ids, int n) {
     LLMI_HIP(hipStreamSynchronize(stream));
     host_next_pos = 0;
     prompt_len = n;
+    sc_m = 0;  // the logits slab holds no row of this prompt
     return LLMI_OK;
 }
 

@@ -28,6 +28,7 @@ int Batch::init(const llmi_config& cfg, int n_seq, int dev) {
     for (int i = 0; i < n_seq; ++i) {
         r.emplace_back(new Engine());
         LLMI_TRY(r.back()->init(cfg, dev, nullptr, stream, i ? r[0].get() : nullptr, false));
+        if (i) r.back()->pf_from = r[0].get();  // one prefill scratch per batch, slot 0's
     }
     return LLMI_OK;
 }
@@ -133,6 +134,14 @@ int Batch::decode(int n, int use_graph) {
     }
     for (int s : act) r[s]->host_next_pos += n;
     return LLMI_OK;
+}
+
+// slot seq's prefill / scored prefill on the batch's stream, through slot 0's prefill scratch;
+// the slot ends where n decode steps would have left it (host_next_pos: the next step's key)
+int Batch::prefill(int seq, int n, int split, bool scored) {
+    LLMI_TRY(slot_ok(seq));
+    LLMI_REQUIRE(r[seq]->prompt_len > 0, "batch prefill: the slot is idle (set_prompt first)");
+    return r[seq]->prefill(n, split, scored);
 }
 
 }  // namespace llmi

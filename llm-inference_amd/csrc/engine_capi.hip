@@ -173,6 +173,19 @@ int llmi_engine_prefill(llmi_engine* e, int n_tokens, int exact) {
     return e->e.prefill(n_tokens, exact == 2 ? 3 : exact ? 2 : 1);
 }
 
+int llmi_engine_prefill_scored(llmi_engine* e, int n_tokens, int exact) {
+    LLMI_REQUIRE(e, "null engine");
+    LLMI_REQUIRE(exact >= 0 && exact <= 2, "prefill: exact must be 0 (fp16 A), 1 (fp32-faithful) or 2 (fp8 lo planes)");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.prefill(n_tokens, exact == 2 ? 3 : exact ? 2 : 1, true);
+}
+
+int llmi_engine_scored_logits(llmi_engine* e, int pos, float* out, int n) {
+    LLMI_REQUIRE(e, "scored_logits: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.scored_logits_out(pos, out, n);
+}
+
 int llmi_engine_sync(llmi_engine* e) {
     LLMI_REQUIRE(e, "null engine");
     LLMI_HIP(hipStreamSynchronize(e->e.stream));
@@ -504,6 +517,13 @@ int llmi_batch_decode(llmi_batch* b, int n_steps, int use_graph) {
     LLMI_REQUIRE(b, "null batch");
     LLMI_HIP(hipSetDevice(b->b.r[0]->device));
     return b->b.decode(n_steps, use_graph);
+}
+
+int llmi_batch_prefill(llmi_batch* b, int seq, int n_tokens, int exact, int scored) {
+    LLMI_REQUIRE(b, "null batch");
+    LLMI_REQUIRE(exact >= 0 && exact <= 2, "prefill: exact must be 0 (fp16 A), 1 (fp32-faithful) or 2 (fp8 lo planes)");
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    return b->b.prefill(seq, n_tokens, exact == 2 ? 3 : exact ? 2 : 1, scored != 0);
 }
 
 int llmi_batch_tokens(llmi_batch* b, int seq, int32_t* out, int n, int* n_valid) {

@@ -3,7 +3,9 @@
 // (context_decoder.cpp:47-143): prompt rows [p0, p0 + n) in chunks of up to
 // kPrefillRows through the MFMA GEMMs and the causal prefill attention, KV
 // slots written; then the last row's final norm + lm_head + argmax, leaving
-// the decode state exactly where n decode steps would have left it. See engine.h.
+// the decode state exactly where n decode steps would have left it. The scored form also
+// runs the final norm + lm_head GEMM over every chunk's rows and fills their logprob
+// records. See engine.h.
 #include "engine.h"
 
 namespace llmi {
@@ -172,21 +174,89 @@ int Engine::prefill_flush(int m) {  // pending down slices into x (after the las
     return LLMI_OK;
 }
 
-int Engine::prefill(int n, int split) {
+// ------------------------------------------------------- scored prefill
+// scored: after each chunk's layers, the final norm + an lm_head GEMM over the chunk's rows
+// into the logits slab, then one logprob launch: row p writes record p + 1 with the scored
+// id prompt[p + 1], every row but the call's last (whose record is rec_head's, as ever).
+// Only the records, the activation planes and the slab are written.
+int Engine::alloc_score() {
+    if (sc_logits) return LLMI_OK;
+    LLMI_HIP(hipMalloc(&sc_logits, (size_t)pf_rows * c.vocab * 4));
+    return LLMI_OK;
+}
+// the scratch of this call: the engine's own, or -- a batch slot -- slot 0's, lent like the
+// weights (one stream serialises its use). The e4m3 copies follow slot 0's weight reloads.
+int Engine::prefill_scratch(int split, bool scored) {
+    Engine& o = pf_from ? *pf_from : *this;
+    LLMI_TRY(o.alloc_prefill());
+    if (split == 3) LLMI_TRY(o.alloc_w8());
+    if (scored) LLMI_TRY(o.alloc_score());
+    if (&o == this) return LLMI_OK;
+    pf = o.pf; pf_rows = o.pf_rows; pf_split_floats = o.pf_split_floats; n_cu = o.n_cu;
+    pf_x = o.pf_x; pf_qkv = o.pf_qkv; pf_o = o.pf_o; pf_act = o.pf_act; pf_ah = o.pf_ah; pf_al = o.pf_al;
+    pf_slab = o.pf_slab; pf_split = o.pf_split; sc_logits = o.sc_logits;
+    if (split == 3) w8l = o.w8l; else w8l.clear();
+    return LLMI_OK;
+}
+bool Engine::head_gemm_supported(bool use_gemm2) const {
+    return use_gemm2 ? gemm2_supported(c.vocab, c.hidden, EPI_STORE)
+                     : gemm_supported(edt, c.vocab, c.hidden, EPI_STORE);
+}
+// rows [p0, p0 + m) of pf_x (flushed): logits of all m rows, records of all but the call's last
+int Engine::score_chunk(int m, int p0, int split, bool use_gemm2, bool last) {
+    const int H = c.hidden;
+    if (use_gemm2) {  // the path the layers took: planes, then the LDS-DMA GEMM (no e4m3 lm_head: two fp16 planes)
+        _Float16* lo = split >= 2 ? pf_al : nullptr;
+        LLMI_TRY(rows_split_launch(pf_x, H, m, H, final_norm, edt, c.rms_eps, pf_ah, lo, H, stream));
+        Gemm2Args g;
+        g.a[0] = pf_ah; g.a[1] = lo; g.planes = lo ? 2 : 1; g.lda = H; g.m = m;
+        g.w = lm_head; g.n = c.vocab; g.k = H;
+        g.epi = EPI_STORE; g.y = sc_logits; g.ldy = c.vocab;
+        LLMI_TRY(gemm2_launch(g, stream));
+    } else {  // the norm fused; int8 engines too (their lm_head is fp16)
+        GemmArgs g;
+        g.split = split == 1 ? 1 : 2;
+        g.w_dtype = edt;
+        g.m = m;
+        g.a = pf_x; g.lda = H; g.gamma = final_norm; g.g_dtype = edt; g.eps = c.rms_eps;
+        g.w = lm_head; g.n = c.vocab; g.k = H;
+        g.epi = EPI_STORE; g.y = sc_logits; g.ldy = c.vocab;
+        LLMI_TRY(gemm_launch(g, stream));
+    }
+    sc_p0 = p0;
+    sc_m = m;
+    const int rows = last ? m - 1 : m;
+    if (rows == 0) return LLMI_OK;
+    return engine_logprob_rows_launch(sc_logits, rows, c.vocab, prompt, p0 + 1, c.max_seq, lp_top, lp_tok(), lp_ids(),
+                                      lp_tlp(), stream);
+}
+// test / debug read-back: the slab row of prompt position pos
+int Engine::scored_logits_out(int pos, float* out, int n) {
+    LLMI_REQUIRE(out && n >= 0 && n <= c.vocab, "scored_logits: bad arguments");
+    LLMI_REQUIRE(sc_logits && sc_m > 0 && pos >= sc_p0 && pos < sc_p0 + sc_m,
+                 "scored_logits: no scored chunk holds this position");
+    LLMI_HIP(hipStreamSynchronize(stream));
+    LLMI_HIP(hipMemcpy(out, sc_logits + (size_t)(pos - sc_p0) * c.vocab, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return LLMI_OK;
+}
+
+int Engine::prefill(int n, int split, bool scored) {
     LLMI_REQUIRE(!grouped && c.tp_world == 1, "prefill: tensor-parallel prefill is not supported");
     LLMI_REQUIRE(prompt_len > 0, "prefill: set_prompt first");
     LLMI_REQUIRE(n >= 1 && host_next_pos + n <= prompt_len, "prefill: rows must lie inside the prompt");
     LLMI_REQUIRE(split >= 1 && split <= 3,
                  "prefill: split must be 1 (fp16 A), 2 (fp32-faithful) or 3 (fp16 hi + fp8 lo planes)");
+    LLMI_REQUIRE(!scored || (lp_top >= 0 && lp_buf), "prefill_scored: set_logprobs first");
     if (!gemm_supported(wdt, ql + 2 * kvrows, c.hidden, EPI_STORE) || !gemm_supported(wdt, c.hidden, ql, EPI_ADD) ||
         !gemm_supported(wdt, 2 * il, c.hidden, EPI_SILU_MUL) || !gemm_supported(wdt, c.hidden, il, EPI_ADD))
         return decode(n, 1);  // fp32 weights / odd shapes: the decode kernels, one row at a time
-    LLMI_TRY(alloc_prefill());
     const bool use_gemm2 = wdt == LLMI_F16 && gemm2_supported(ql + 2 * kvrows, c.hidden, EPI_STORE) &&
                            gemm2_supported(c.hidden, ql, EPI_ADD) && gemm2_supported(2 * il, c.hidden, EPI_SILU_MUL) &&
                            gemm2_supported(c.hidden, il, EPI_ADD) && c.head_dim % 64 == 0;
+    // no GEMM form for the lm_head shape: decode steps, which score every row themselves
+    if (scored && !head_gemm_supported(use_gemm2)) return decode(n, 1);
     if (split == 3 && !(use_gemm2 && lo8_supported())) split = 2;  // shapes without the fp8 lo pass: exact planes
-    if (split == 3) LLMI_TRY(alloc_w8());
+    LLMI_TRY(prefill_scratch(split, scored));
     const int H = c.hidden, p_begin = host_next_pos;
     for (int p0 = p_begin; p0 < p_begin + n; p0 += pf_rows) {
         const int m = std::min(pf_rows, p_begin + n - p0);
@@ -228,6 +298,7 @@ int Engine::prefill(int n, int split) {
         LLMI_TRY(prefill_flush(m));
         if (p0 + m == p_begin + n)  // last row -> x for the final norm + lm_head
             LLMI_HIP(hipMemcpyAsync(x, pf_x + (size_t)(m - 1) * H, (size_t)H * 4, hipMemcpyDeviceToDevice, stream));
+        if (scored) LLMI_TRY(score_chunk(m, p0, split, use_gemm2, p0 + m == p_begin + n));
     }
     // the decode state first (cur_pos = last prompt row), then the head exactly as a
     // decode step runs it -- lm_head + argmax keys, and the top-K draw at step

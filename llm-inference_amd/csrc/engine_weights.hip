@@ -20,7 +20,10 @@ Engine::~Engine() {  // teardown errors are not actionable; ignore them explicit
     if (kcache) (void)hipFree(kcache);
     if (vcache) (void)hipFree(vcache);
     if (scratch) (void)hipFree(scratch);
-    if (pf) (void)hipFree(pf);
+    if (!pf_from) {  // (a batch slot's are slot 0's)
+        if (pf) (void)hipFree(pf);
+        if (sc_logits) (void)hipFree(sc_logits);
+    }
     if (w8blob) (void)hipFree(w8blob);
     if (rl_acc) (void)hipFree(rl_acc);
     if (rl_cnt) (void)hipFree(rl_cnt);

@@ -535,6 +535,11 @@ int engine_logprob_check(int vocab, int n_top);
 int engine_logprob_launch(const struct DecodeState* st, const float* logits, int vocab, const int32_t* prompt,
                           const unsigned long long* partials, int np, int max_seq, int n_top, float* tok_lp,
                           int32_t* top_ids, float* top_lp, hipStream_t s);
+// row-record form (the scored prefill): block b reads row b of slab [rows][vocab] and writes
+// record rec0 + b (rec0 >= 1, rec0 + rows <= max_seq) with the scored id prompt[rec0 + b] (an
+// id outside [0, vocab) scores id 0). The ids are the engine's own: no host check, no sync.
+int engine_logprob_rows_launch(const float* slab, int rows, int vocab, const int32_t* prompt, int rec0, int max_seq,
+                               int n_top, float* tok_lp, int32_t* top_ids, float* top_lp, hipStream_t s);
 int repeat_kv_launch(const void* k_cache, const void* v_cache, int dtype, int layer, const int* ctx_len, int batch,
                      int kv_heads, int max_seq, int heads, int max_k_len, int d, void* k_dst, void* v_dst,
                      hipStream_t s);

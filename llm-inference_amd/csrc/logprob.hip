@@ -45,6 +45,8 @@ struct LpArgs {
     const unsigned long long* partials;
     int np;
     int max_seq;
+    // row-record form (the scored prefill): rec0 > 0, block b = record rec0 + b, id prompt[rec0 + b]
+    int rec0;
 };
 
 struct LpScratch {
@@ -135,6 +137,10 @@ __global__ __launch_bounds__(kRowThreads) void logprob_kernel(LpArgs a) {
         }
         if (tok < 0 || tok >= V) tok = 0;  // as step_start_kernel (which also raises the error flag)
         if (rec > a.max_seq) return;       // uniform; the host guards this
+    } else if (a.rec0 > 0) {
+        rec = a.rec0 + b;
+        tok = a.prompt[rec];
+        if (tok < 0 || tok >= V) tok = 0;  // as the engine form
     } else if (a.ids) {
         tok = a.ids[b];
     }
@@ -232,6 +238,17 @@ int engine_logprob_launch(const DecodeState* st, const float* logits, int vocab,
     a.logits = logits; a.vocab = vocab; a.n_top = n_top; a.out_lp = tok_lp; a.top_ids = top_ids; a.top_lp = top_lp;
     a.st = st; a.prompt = prompt; a.partials = partials; a.np = np; a.max_seq = max_seq;
     return logprob_dispatch(a, 1, s);
+}
+
+int engine_logprob_rows_launch(const float* slab, int rows, int vocab, const int32_t* prompt, int rec0, int max_seq,
+                               int n_top, float* tok_lp, int32_t* top_ids, float* top_lp, hipStream_t s) {
+    LLMI_REQUIRE(slab && prompt && tok_lp && rows >= 1, "engine_logprob_rows: bad arguments");
+    LLMI_REQUIRE(rec0 >= 1 && rec0 + rows <= max_seq, "engine_logprob_rows: records must lie inside the prompt");
+    LLMI_REQUIRE(n_top == 0 || (top_ids && top_lp), "engine_logprob_rows: n_top > 0 needs top_ids and top_lp");
+    LpArgs a{};
+    a.logits = slab; a.vocab = vocab; a.n_top = n_top; a.out_lp = tok_lp; a.top_ids = top_ids; a.top_lp = top_lp;
+    a.prompt = prompt; a.rec0 = rec0; a.max_seq = max_seq;
+    return logprob_dispatch(a, rows, s);
 }
 
 }  // namespace llmi

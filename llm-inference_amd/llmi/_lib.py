@@ -155,6 +155,8 @@ _SIGS = {
     "llmi_engine_set_prompt": (_I, [_P, _P, _I]),
     "llmi_engine_decode": (_I, [_P, _I, _I]),
     "llmi_engine_prefill": (_I, [_P, _I, _I]),
+    "llmi_engine_prefill_scored": (_I, [_P, _I, _I]),
+    "llmi_engine_scored_logits": (_I, [_P, _I, _P, _I]),
     "llmi_engine_sync": (_I, [_P]),
     "llmi_engine_tokens": (_I, [_P, _P, _I, C.POINTER(_I)]),
     "llmi_engine_logits": (_I, [_P, _P, _I]),
@@ -195,6 +197,7 @@ _SIGS = {
     "llmi_batch_set_logprobs": (_I, [_P, _I, _I]),
     "llmi_batch_logprobs": (_I, [_P, _I, _P, _P, _P, _I, C.POINTER(_I), C.POINTER(_I)]),
     "llmi_batch_decode": (_I, [_P, _I, _I]),
+    "llmi_batch_prefill": (_I, [_P, _I, _I, _I, _I]),
     "llmi_batch_tokens": (_I, [_P, _I, _P, _I, C.POINTER(_I)]),
     "llmi_batch_logits": (_I, [_P, _I, _P, _I]),
     "llmi_batch_sync": (_I, [_P]),

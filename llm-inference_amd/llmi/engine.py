@@ -105,17 +105,23 @@ class Engine:
         consumed)."""
         return _read_logprobs("llmi_engine_logprobs", (self._h,), self.cfg.max_seq + 1 if n is None else int(n))
 
-    def score(self, ids, use_graph: bool = True) -> np.ndarray:
+    def score(self, ids, use_graph: bool = True, prefill: bool = False, exact=True) -> np.ndarray:
         """Log-likelihood of a given text: logprob of ids[p] given ids[:p] for p = 1 .. len - 1
         (fp32 [len - 1]; their negated mean is the log-perplexity). Steps the text through
-        len - 1 decode steps; turns logprobs on (n_top 0) for the call if they are off."""
+        len - 1 decode steps, or -- prefill=True -- runs it as one scored prefill of len - 1
+        rows (no token step; `exact` as in prefill); turns logprobs on (n_top 0) for the call
+        if they are off."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         was = self._lp_top
         if was < 0:
             self.set_logprobs(0)
         try:
             self.set_prompt(ids)
-            self.decode(len(ids) - 1, use_graph)
+            if prefill:
+                if len(ids) > 1:
+                    self.prefill(len(ids) - 1, exact, score=True)
+            else:
+                self.decode(len(ids) - 1, use_graph)
             return self.logprobs(len(ids))[0][1:]
         finally:
             if was < 0:
@@ -141,13 +147,22 @@ class Engine:
     def decode(self, n_steps: int, use_graph: bool = True):
         call("llmi_engine_decode", self._h, n_steps, 1 if use_graph else 0)
 
-    def prefill(self, n_tokens: int, exact=True):
+    def prefill(self, n_tokens: int, exact=True, score: bool = False):
         """exact: True / 1 fp32-faithful (two fp16 planes), 2 fp16 hi + e4m3 lo planes on
-        the fp8 MFMA (~1e-4), False / 0 fp16 activations (llmi_engine_prefill)."""
+        the fp8 MFMA (~1e-4), False / 0 fp16 activations (llmi_engine_prefill). score: also
+        fill the logprob records of the rows consumed (llmi_engine_prefill_scored; needs
+        set_logprobs); everything else is bitwise the unscored call's."""
         mode = int(exact)
         if mode not in (0, 1, 2):
             raise ValueError("prefill: exact must be False/0, True/1 or 2")
-        call("llmi_engine_prefill", self._h, n_tokens, mode)
+        call("llmi_engine_prefill_scored" if score else "llmi_engine_prefill", self._h, n_tokens, mode)
+
+    def scored_logits(self, pos: int) -> np.ndarray:
+        """Test / debug: the fp32 logits row of prompt position pos as the last scored prefill
+        chunk's lm_head GEMM left it (llmi_engine_scored_logits)."""
+        out = np.zeros(self.cfg.vocab, np.float32)
+        call("llmi_engine_scored_logits", self._h, int(pos), out.ctypes.data, self.cfg.vocab)
+        return out
 
     def sync(self):
         call("llmi_engine_sync", self._h)
@@ -322,6 +337,8 @@ class Batch:
         call("llmi_batch_create", C.byref(cfg), n_seq, device, C.byref(h))
         self._h = h
         self._lp_top = [-1] * n_seq
+        self._plen = [0] * n_seq  # each slot's prompt length (0: idle) and next position
+        self._pos = [0] * n_seq
 
     def close(self):
         if getattr(self, "_h", None):
@@ -351,10 +368,24 @@ class Batch:
         """(Re)start slot seq with this prompt; the other slots are left where they are."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)
         call("llmi_batch_set_prompt", self._h, int(seq), ids.ctypes.data, len(ids))
+        self._plen[int(seq)], self._pos[int(seq)] = len(ids), 0
 
     def reset(self, seq: int):
         """Make slot seq idle (its buffers keep their contents)."""
         call("llmi_batch_reset", self._h, int(seq))
+        self._plen[int(seq)], self._pos[int(seq)] = 0, 0
+
+    def prefill(self, seq: int, n: Optional[int] = None, exact=True, score: bool = False):
+        """Engine.prefill for one slot (llmi_batch_prefill): its next n prompt rows (None: the
+        rest of its prompt) in one batched pass on the batch's stream; the other slots are
+        untouched, and the next decode steps the slot with them. score: Engine.prefill's."""
+        seq, mode = int(seq), int(exact)
+        if mode not in (0, 1, 2):
+            raise ValueError("prefill: exact must be False/0, True/1 or 2")
+        if n is None and 0 <= seq < self.n_seq:
+            n = self._plen[seq] - self._pos[seq]
+        call("llmi_batch_prefill", self._h, seq, int(n or 0), mode, 1 if score else 0)
+        self._pos[seq] += int(n)
 
     def set_sampling_params(self, seq: int, top_k: int = 0, top_p: float = 1.0, temperature: float = 1.0,
                             repetition_penalty: float = 1.0, seed: int = 0):
@@ -371,10 +402,11 @@ class Batch:
         return _read_logprobs("llmi_batch_logprobs", (self._h, int(seq)),
                               self.cfg.max_seq + 1 if n is None else int(n))
 
-    def score(self, texts, use_graph: bool = True) -> list:
+    def score(self, texts, use_graph: bool = True, prefill: bool = False) -> list:
         """Engine.score over up to n_seq texts of different lengths at once: slot i steps
-        texts[i] (None: idle) and goes idle when its text ends. Returns one fp32 [len - 1]
-        array per text. Slots with logprobs off have them on (n_top 0) for the call."""
+        texts[i] (None: idle) and goes idle when its text ends; prefill=True: one scored slot
+        prefill per text instead (bitwise Engine.score(t, prefill=True)). Returns one fp32
+        [len - 1] array per text. Slots with logprobs off have them on (n_top 0) for the call."""
         if len(texts) > self.n_seq:
             raise ValueError("score: more texts than slots")
         was = list(self._lp_top)
@@ -389,6 +421,12 @@ class Batch:
                 if was[i] < 0:
                     self.set_logprobs(i, 0)
                 self.set_prompt(i, t)
+                if prefill:
+                    if len(t) > 1:
+                        self.prefill(i, len(t) - 1, score=True)
+                    out[i] = self.logprobs(i, len(t))[0][1:]
+                    self.reset(i)
+                    continue
                 left[i] = len(t) - 1
             while left:
                 n = min(left.values())
@@ -408,6 +446,9 @@ class Batch:
     def decode(self, n_steps: int, use_graph: bool = True):
         """Every active slot advances n_steps tokens."""
         call("llmi_batch_decode", self._h, int(n_steps), 1 if use_graph else 0)
+        for i in range(self.n_seq):
+            if self._plen[i] > 0:
+                self._pos[i] += int(n_steps)
 
     def sync(self):
         call("llmi_batch_sync", self._h)
@@ -430,10 +471,11 @@ class Batch:
         call("llmi_batch_bytes", self._h, C.byref(w), C.byref(kv))
         return w.value, kv.value
 
-    def generate(self, prompts, n_new: int, use_graph: bool = True) -> list:
+    def generate(self, prompts, n_new: int, use_graph: bool = True, prefill: bool = False) -> list:
         """Greedy (or each slot's sampler): slot i takes prompts[i] (None: idle) and produces
-        n_new tokens; prompts are consumed by decode steps. A slot that has its n_new tokens
-        goes idle while longer prompts finish. Returns one id array per slot (None: idle)."""
+        n_new tokens; prompts are consumed by decode steps, or -- prefill=True -- by one slot
+        prefill each. A slot that has its n_new tokens goes idle while longer prompts finish.
+        Returns one id array per slot (None: idle)."""
         if len(prompts) > self.n_seq:
             raise ValueError("generate: more prompts than slots")
         left, out = {}, [None] * len(prompts)
@@ -444,7 +486,9 @@ class Batch:
                 continue
             p = np.ascontiguousarray(p, np.int32)
             self.set_prompt(i, p)
-            left[i] = len(p) + n_new - 1
+            if prefill:
+                self.prefill(i)
+            left[i] = (0 if prefill else len(p)) + n_new - 1
         plen = {i: len(prompts[i]) for i in left}
         while left:
             n = min(left.values())
