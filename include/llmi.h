@@ -36,7 +36,8 @@ extern "C" {
 
 typedef void* llmi_stream_t; /* hipStream_t; NULL = legacy default stream */
 
-enum llmi_dtype { LLMI_F32 = 0, LLMI_F16 = 1, LLMI_I8 = 2, LLMI_I32 = 3, LLMI_I64 = 4 };
+/* LLMI_I4: 4-bit group-quantised weights (W4A16; the format is stated at llmi_quantize_groups_i4) */
+enum llmi_dtype { LLMI_F32 = 0, LLMI_F16 = 1, LLMI_I8 = 2, LLMI_I32 = 3, LLMI_I64 = 4, LLMI_I4 = 5 };
 
 #define LLMI_OK 0
 #define LLMI_EINVAL (-1)
@@ -161,7 +162,11 @@ int llmi_debug_stream_k(int mode, int launches);
  * the GEMV is launched once on `stream`. Zero (NULL) means "not used"; the only defaults are
  * eps 0 -> 1e-5 and ksplit 0 -> 1. w_dtype / g_dtype are llmi_dtype values. The caller owns
  * every buffer (device memory).
- *   w [n_rows, ldw (0: k)] with per-row fp16 `scales` for int8; x fp32 [k], or x_fixed int64
+ *   w [n_rows, ldw (0: k)] with per-row fp16 `scales` for int8; w_dtype LLMI_I4: w [n_rows, k / 2]
+ *   nibbles with `scales` fp16 [n_rows][k / 128] (llmi_quantize_groups_i4), k % 128 == 0, and only
+ *   the forms of the token step: x_fixed + RMSNorm with epi 0 or 2, or an fp32 x with epi 4
+ *   (ksplit 1); kpar > 1, ksplit > 1, ldw other than 0 or k, epi 1 and 3, an fp32 gamma and any
+ *   other input form return LLMI_EUNSUPPORTED with nothing launched; x fp32 [k], or x_fixed int64
  *   [k] (value * 2^32) with RMSNorm, whose fp32 image workgroup 0 writes to x_out;
  *   gamma non-NULL: RMSNorm of x (gamma dtype g_dtype: f16 / f32) folded in;
  *   epi 0: y[r] = acc; 1: y[r] = acc + resid_scale * resid[r] (resid may alias y);
@@ -551,6 +556,26 @@ int llmi_synth_fill_host(void* out, int out_dtype, int kind, uint64_t seed, uint
  * col0 + cols <= row_len <= ld; w 16-byte aligned, q 4-byte. */
 int llmi_quantize_rows_i8(const float* w, size_t ld, int rows, int row_len, int col0, int cols, int8_t* q,
                           void* scales /* fp16[rows] */, int32_t* bad_rows, llmi_stream_t stream);
+/* W4A16 quantiser (quant.hip): fp32 w [rows, ld] with row_len data columns, row_len % 128 == 0
+ * -> nibbles q uint8 [rows, row_len / 2] and fp16 scales [rows][row_len / 128], w ~= q * s.
+ * The format, which the int4 GEMV decodes:
+ *   Groups: 128 consecutive columns of one row.
+ *   Scales: one fp16 scale per (row, group), layout s [rows][k / 128], row-major, in a
+ *     separate array.
+ *   Values: q lies in [-7, 7] and is stored as the nibble q + 8, two nibbles per byte, the low
+ *     nibble holding the even column; a 16-byte chunk is 32 consecutive columns and a row is
+ *     k / 2 bytes. The quantiser never writes nibble 0; the kernel decodes nibble 0 as -8.
+ *   Definition (bit-exact against a numpy restatement):
+ *     amax = max |w| over the group;
+ *     s = fp16_rne(fp32(amax / 7)), an fp16 zero becomes 2^-24, an overflow becomes 65504;
+ *     q = clip(rint(fp32(w / fp32(s))), -7, 7), divisions correctly rounded fp32, rint
+ *       round-half-even.
+ *     A row holding a NaN or an infinity gets q = 0 (nibble 8) and s = 0 in every group, and
+ *     counts once in *bad_rows (device counter the caller zeroes; may be NULL).
+ * Whole rows only; [row_len, ld) is padding and never read. All pointers are device pointers;
+ * row_len <= ld, ld a multiple of 4, w 16-byte aligned, q 4-byte, scales 2-byte. */
+int llmi_quantize_groups_i4(const float* w, size_t ld, int rows, int row_len, uint8_t* q,
+                            void* scales /* fp16[rows][row_len / 128] */, int32_t* bad_rows, llmi_stream_t stream);
 /* Device memory for host-side callers that include no HIP headers (the C++
  * mirror in include/llmi/): hipMalloc / hipFree / hipMemcpy / hipDeviceSynchronize.
  * kind: 0 host->device, 1 device->host, 2 device->device. */
@@ -585,7 +610,11 @@ int llmi_synth_prompt(uint64_t seed, int n, int vocab, int32_t* out);
 typedef struct llmi_config {
     int hidden, heads, kv_heads, head_dim, inter, layers, vocab, max_seq;
     float rms_eps, rope_base;
-    int weight_dtype; /* LLMI_F16 (default), LLMI_F32 (reference Llama<float>), LLMI_I8 (W8A16) */
+    int weight_dtype; /* LLMI_F16 (default), LLMI_F32 (reference Llama<float>), LLMI_I8 (W8A16),
+                       * LLMI_I4 (W4A16: q/k/v, gate_up and down in 4-bit groups of 128, W_o W8A16;
+                       * tp_world 1, hidden and inter multiples of 128; decode steps only: prefill,
+                       * the ring layer, llmi_batch_create and llmi_group_create return
+                       * LLMI_EUNSUPPORTED) */
     int kv_dtype;     /* LLMI_F16 (throughput) or LLMI_F32 (parity) */
     int tp_rank, tp_world;
 } llmi_config;
@@ -636,7 +665,9 @@ int llmi_engine_load_tensor(llmi_engine* e, const char* name, const float* host,
  * llmi_quantize_rows_i8 into the engine's int8 weights and fp16 row scales; the column-sharded
  * o_proj and down take each scale from the whole unsharded row, so every TP rank holds the
  * same scales. Norms, lm_head and the embedding are loaded as by llmi_engine_load_bin (fp16).
- * A linear tensor holding a NaN or an infinity fails with a message naming it. */
+ * A linear tensor holding a NaN or an infinity fails with a message naming it.
+ * An LLMI_I4 engine takes the same calls: q/k/v, gate_up and down go through
+ * llmi_quantize_groups_i4 (nibbles + fp16 group scales), o_proj through llmi_quantize_rows_i8. */
 int llmi_engine_load_bin_quantized(llmi_engine* e, const char* weight_path);
 int llmi_engine_load_tensor_quantized(llmi_engine* e, const char* name, const float* host, size_t count);
 /* Llama<T>::Sampling (llama.cpp:245-262: launchTopKforBeamSearch + launchSampling) inside the

@@ -53,7 +53,7 @@ inline TokenLogprobs ReadLogprobs(llmi_engine* eng, int first, int count) {
 
 class LlamaModel {
 public:
-    // preset: "llama2-7b", "llama2-13b", "tiny"; weight_dtype LLMI_F16 / LLMI_F32 / LLMI_I8
+    // preset: "llama2-7b", "llama2-13b", "tiny"; weight_dtype LLMI_F16 / LLMI_F32 / LLMI_I8 / LLMI_I4
     LlamaModel(const std::string& preset, int weight_dtype = LLMI_F16, int kv_dtype = LLMI_F16, int max_seq = 0,
                int device = 0) {
         LLMI_CALL(llmi_config_preset(preset.c_str(), &cfg));
@@ -70,6 +70,7 @@ public:
     // Llama<T>::loadWeights(weight_path) (llama_weights.cc:41-53): weight_path + "<name>.bin", raw fp32
     void loadWeights(const std::string& weight_path) { LLMI_CALL(llmi_engine_load_bin(eng, weight_path.c_str())); }
     // the same files into an LLMI_I8 model: the linear weights are quantised to W8A16 on the device
+    // (an LLMI_I4 model: q/k/v, gate_up and down to 4-bit groups of 128 columns, o_proj to W8A16)
     void loadWeightsQuantized(const std::string& weight_path) {
         LLMI_CALL(llmi_engine_load_bin_quantized(eng, weight_path.c_str()));
     }
@@ -137,7 +138,7 @@ inline std::unique_ptr<LlamaModel> CreateRealLLMModel(const std::string& weight_
                                                       const std::string& preset = "llama2-7b",
                                                       int weight_dtype = LLMI_F16, bool quantize = false) {
     auto m = std::make_unique<LlamaModel>(preset, weight_dtype);
-    if (quantize)  // weight_dtype LLMI_I8: W8A16 from the fp32 files
+    if (quantize)  // weight_dtype LLMI_I8 / LLMI_I4: W8A16 / W4A16 from the fp32 files
         m->loadWeightsQuantized(weight_path);
     else
         m->loadWeights(weight_path);

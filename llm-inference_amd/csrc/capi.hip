@@ -540,6 +540,11 @@ int llmi_quantize_rows_i8(const float* w, size_t ld, int rows, int row_len, int 
                                    STREAM(stream));
 }
 
+int llmi_quantize_groups_i4(const float* w, size_t ld, int rows, int row_len, uint8_t* q, void* scales,
+                            int32_t* bad_rows, llmi_stream_t stream) {
+    return quantize_groups_i4_launch(w, ld, rows, row_len, q, static_cast<__half*>(scales), bad_rows, STREAM(stream));
+}
+
 int llmi_synth_fill_host(void* out, int out_dtype, int kind, uint64_t seed, uint32_t tid, int rows, int cols,
                          int row0, int col0, int ld) {
     return synth_fill_host(out, out_dtype, kind, seed, tid, rows, cols, row0, col0, ld);

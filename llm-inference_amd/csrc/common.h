@@ -54,6 +54,8 @@ inline size_t dtype_size(int dt) {
         default: return 0;
     }
 }
+// bytes of one row of `cols` weights (LLMI_I4 packs two a byte: dtype_size cannot say it)
+inline size_t row_bytes(int dt, size_t cols) { return dt == LLMI_I4 ? cols / 2 : cols * dtype_size(dt); }
 
 // ------------------------------------------------------------ device math
 __device__ __forceinline__ float to_f32(float v) { return v; }

@@ -138,7 +138,16 @@ struct Engine {
     int hl = 0, kvl = 0, ql = 0, kvrows = 0, il = 0, vl = 0;
     int wdt = LLMI_F16;      // linear weight dtype
     int edt = LLMI_F16;      // embedding / lm_head / norm dtype
-    size_t wsz = 2, esz = 2;
+    size_t wsz = 2, esz = 2;  // (wsz 0 for int4: weight sizes go through lin_bytes)
+    // int4 engines keep W_o W8A16 (8.3 % of a layer; the o_proj kernel's 16-lane head slices)
+    int odt() const { return wdt == LLMI_I4 ? LLMI_I8 : wdt; }
+    bool quantised() const { return wdt == LLMI_I8 || wdt == LLMI_I4; }
+    // bytes of a [rows, cols] linear weight of dtype dt, and of its fp16 scales (int8: one a
+    // row; int4: one a 128-column group)
+    static uint64_t lin_bytes(int dt, uint64_t rows, uint64_t cols) { return rows * row_bytes(dt, cols); }
+    static uint64_t scale_bytes(int dt, uint64_t rows, uint64_t cols) {
+        return dt == LLMI_I8 ? rows * 2 : dt == LLMI_I4 ? rows * (cols / 128) * 2 : 0;
+    }
     int n_cu = 0;
     uint64_t seed = 0;
 
@@ -310,11 +319,15 @@ struct Engine {
     int alloc_state();
     int weights_changed();
     int load_synthetic(uint64_t sd);
+    int load_synthetic_i4();
     static int put_host(void* dst, int dt, const float* src, size_t src_ld, int rows, int cols, size_t row0,
                         size_t col0, hipStream_t s);
     void quant_release();
+    int quant_stage(size_t row_bytes, int rows, int* chunk);
+    int quant_rows(const float* rows_dev, size_t ld, int n, int cols, void* q_dst, __half* s_dst, size_t q_row, int qdt,
+                   int32_t* bad, int col0 = 0);
     int quant_put(const std::string& nm, const float* src, size_t src_ld, size_t row0, int rows, int col0, int cols,
-                  void* q_dst, size_t q_row_off, __half* s_dst);
+                  void* q_dst, size_t q_row_off, __half* s_dst, int qdt);
     int load_tensor(const char* name, const float* src, size_t count, bool quantize = false);
     int load_tensor_impl(const char* name, const float* src, size_t count, bool quantize);
     int load_bin(const char* weight_path, bool quantize = false);

@@ -38,7 +38,7 @@ int Engine::kpar_of(int groups) const {
     if (c.tp_world == 1 || kpar_off) return 0;
     // the K-parted kernel stages x for k <= 5120 and splits a row's 16-B chunks evenly
     // (a wider model must fall back to kpar 0, not fail the launch)
-    const int epl = wdt == LLMI_I8 ? 16 : wdt == LLMI_F16 ? 8 : 4;
+    const int epl = wdt == LLMI_I8 ? 16 : wdt == LLMI_F16 ? 8 : 4;  // (int4: tp_world 1 only, returned above)
     if (c.hidden > 5120 || c.hidden % epl != 0) return 0;
     const int cus = n_cu > 0 ? n_cu : 256;
     const int blocks = (groups + 3) / 4;
@@ -83,7 +83,7 @@ OprojArgs Engine::o_args(int l) const {
     const Layer& L = layers[l];
     OprojArgs a;
     a.stamps = stamp_ptr();
-    a.w = L.o; a.scales = L.o_s; a.w_dtype = wdt;
+    a.w = L.o; a.scales = L.o_s; a.w_dtype = odt();  // (int4 engines: W_o is W8A16)
     a.head_major = 0;
     a.n_rows = c.hidden; a.ldw = ql;
     a.heads = hl; a.head_dim = c.head_dim; a.max_seq = c.max_seq;
@@ -384,6 +384,10 @@ bool Engine::ring_ok() const {
 int Engine::set_decode_mode(int mode) {
     LLMI_REQUIRE(mode == 0 || mode == 1, "set_decode_mode: mode must be 0 (launches) or 1 (ring layer)");
     LLMI_HIP(hipStreamSynchronize(stream));
+    if (mode == 1 && wdt == LLMI_I4) {
+        set_last_error("[llmi][ERROR] set_decode_mode: the ring layer streams fp16 weights; int4 engines run mode 0");
+        return LLMI_EUNSUPPORTED;
+    }
     if (mode == 1) {
         if (n_cu == 0) LLMI_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
         if (!ring_ok()) {

@@ -23,6 +23,10 @@ int Batch::init(const llmi_config& cfg, int n_seq, int dev) {
         set_last_error("[llmi][ERROR] batch: tensor-parallel batches are not built (tp_world must be 1)");
         return LLMI_EUNSUPPORTED;
     }
+    if (cfg.weight_dtype == LLMI_I4) {
+        set_last_error("[llmi][ERROR] batch: int4 weights are not built into the multi-row GEMV (use an Engine)");
+        return LLMI_EUNSUPPORTED;
+    }
     LLMI_HIP(hipSetDevice(dev));
     LLMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     for (int i = 0; i < n_seq; ++i) {

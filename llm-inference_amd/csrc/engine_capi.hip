@@ -557,8 +557,7 @@ int llmi_batch_bytes(llmi_batch* b, uint64_t* weight_bytes_per_step, uint64_t* k
     const Engine& g = *b->b.r[0];
     const uint64_t n_act = b->b.active().size();
     // the weights once; W_o (+ its int8 row scales) once more for every further active slot
-    uint64_t wo = (uint64_t)g.c.hidden * g.ql * g.wsz;
-    if (g.wdt == LLMI_I8) wo += (uint64_t)g.c.hidden * 2;
+    const uint64_t wo = Engine::lin_bytes(g.odt(), g.c.hidden, g.ql) + Engine::scale_bytes(g.odt(), g.c.hidden, g.ql);
     if (weight_bytes_per_step)
         *weight_bytes_per_step = g.stream_bytes + (n_act > 1 ? (n_act - 1) * wo * g.c.layers : 0);
     if (kv_bytes_per_pos)

@@ -12,6 +12,10 @@ Group::~Group() {
 
 int Group::init(const llmi_config& cfg, int world, int dev) {
     LLMI_REQUIRE(world >= 1 && world <= 64, "group: world must be 1..64");
+    if (cfg.weight_dtype == LLMI_I4) {
+        set_last_error("[llmi][ERROR] group: int4 weights run on a single-rank engine only (no tensor parallel)");
+        return LLMI_EUNSUPPORTED;
+    }
     LLMI_HIP(hipSetDevice(dev));
     LLMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     for (int i = 0; i < world; ++i) {

@@ -241,6 +241,10 @@ int Engine::scored_logits_out(int pos, float* out, int n) {
 }
 
 int Engine::prefill(int n, int split, bool scored) {
+    if (wdt == LLMI_I4) {
+        set_last_error("[llmi][ERROR] prefill: int4 engines have no prefill GEMMs (run the prompt as decode steps)");
+        return LLMI_EUNSUPPORTED;
+    }
     LLMI_REQUIRE(!grouped && c.tp_world == 1, "prefill: tensor-parallel prefill is not supported");
     LLMI_REQUIRE(prompt_len > 0, "prefill: set_prompt first");
     LLMI_REQUIRE(n >= 1 && host_next_pos + n <= prompt_len, "prefill: rows must lie inside the prompt");

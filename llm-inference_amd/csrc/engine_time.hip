@@ -72,10 +72,11 @@ int llmi_engine_time_kernel(llmi_engine* e, int which, int iters, float* avg_us,
                  "time_kernel: the all-reduce needs an RCCL communicator (tp_id)");
     LLMI_REQUIRE(which < 8 || which > 9 || g.peers_ready, "time_kernel: the one-shot exchange needs xchg_open");
     LLMI_REQUIRE(which != 10 || (g.decode_mode == 1 && g.wdt_valid), "time_kernel: the ring layer needs decode mode 1");
-    const uint64_t ws = g.wsz, sc = (g.wdt == LLMI_I8) ? 2 : 0;
-    auto qkv_bytes = [&]() -> uint64_t {
-        return (uint64_t)(g.ql + 2 * g.kvrows) * H * ws + (g.ql + 2 * g.kvrows) * sc;
+    // a [rows, cols] linear weight of dtype dt with its scales
+    auto lin = [&](int dt, uint64_t rows, uint64_t cols) -> uint64_t {
+        return Engine::lin_bytes(dt, rows, cols) + Engine::scale_bytes(dt, rows, cols);
     };
+    auto qkv_bytes = [&]() -> uint64_t { return lin(g.wdt, g.ql + 2 * g.kvrows, H); };
     auto attn_bytes = [&](uint64_t* out) -> int {  // the K/V rows read up to the device's position, one row written
         llmi::DecodeState hs;
         LLMI_HIP(hipMemcpy(&hs, g.st, sizeof(hs), hipMemcpyDeviceToHost));
@@ -86,15 +87,17 @@ int llmi_engine_time_kernel(llmi_engine* e, int which, int iters, float* avg_us,
     switch (which) {
         case 0: b = qkv_bytes(); break;
         case 1: LLMI_TRY(attn_bytes(&b)); break;
-        case 2: b = (uint64_t)H * g.ql * ws + H * sc; break;
-        case 3: b = (uint64_t)2 * g.il * H * ws + 2 * g.il * sc; break;
-        case 4: b = (uint64_t)H * g.il * ws + H * sc; break;
+        case 2: b = lin(g.odt(), H, g.ql); break;
+        case 3: b = lin(g.wdt, 2 * g.il, H); break;
+        case 4: b = lin(g.wdt, H, g.il); break;
         case 5: b = (uint64_t)g.vl * H * g.esz; break;
         case 6:
         case 7:
         case 8:
         case 9: b = (uint64_t)H * 8; break;
-        case 10: b = ((uint64_t)H * g.ql + 3ull * g.il * H + (uint64_t)(g.ql + 2 * g.kvrows) * H) * ws; break;
+        case 10:  // (fp16 only: no scales)
+            b = lin(g.wdt, H, g.ql) + lin(g.wdt, 3ull * g.il, H) + lin(g.wdt, g.ql + 2 * g.kvrows, H);
+            break;
         case 11:
             LLMI_TRY(attn_bytes(&b));
             b += qkv_bytes();

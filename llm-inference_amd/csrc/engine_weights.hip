@@ -1,5 +1,5 @@
 // Engine setup and teardown, the weight layout, and the three loaders (synthetic, the
-// reference's fp32 files, W8A16 quantised on load). See engine.h.
+// reference's fp32 files, W8A16 / W4A16 quantised on load). See engine.h.
 #include "engine.h"
 #include "prng.h"
 
@@ -51,9 +51,14 @@ int Engine::init(const llmi_config& cfg, int dev, const void* tp_id, hipStream_t
     LLMI_REQUIRE(c.max_seq > 0 && c.layers > 0 && c.vocab > 0, "engine: bad dims");
     LLMI_REQUIRE(c.kv_dtype == LLMI_F16 || c.kv_dtype == LLMI_F32, "engine: kv dtype must be f16/f32");
     wdt = c.weight_dtype;
-    LLMI_REQUIRE(wdt == LLMI_F16 || wdt == LLMI_F32 || wdt == LLMI_I8, "engine: bad weight dtype");
+    LLMI_REQUIRE(wdt == LLMI_F16 || wdt == LLMI_F32 || wdt == LLMI_I8 || wdt == LLMI_I4, "engine: bad weight dtype");
+    if (wdt == LLMI_I4 && (W != 1 || ext_stream != nullptr)) {
+        set_last_error("[llmi][ERROR] engine: int4 weights run on a single-rank engine only (tp_world 1, no "
+                       "in-process group, no batch)");
+        return LLMI_EUNSUPPORTED;
+    }
     edt = (wdt == LLMI_F32) ? LLMI_F32 : LLMI_F16;
-    wsz = dtype_size(wdt);
+    wsz = dtype_size(wdt);  // (0 for int4: sizes go through row_bytes / lin_bytes)
     esz = dtype_size(edt);
     hl = c.heads / W;
     kvl = c.kv_heads / W;
@@ -61,9 +66,14 @@ int Engine::init(const llmi_config& cfg, int dev, const void* tp_id, hipStream_t
     kvrows = kvl * c.head_dim;
     il = c.inter / W;
     vl = c.vocab / W;
-    const int epl = 16 / (int)wsz;
-    LLMI_REQUIRE(c.hidden % epl == 0 && ql % epl == 0 && il % epl == 0,
-                 "engine: hidden, q rows per rank and inter per rank must be multiples of 16 bytes");
+    if (wdt == LLMI_I4) {  // whole 128-column groups in q/k/v, gate_up and down; W_o is int8
+        LLMI_REQUIRE(c.hidden % 128 == 0 && il % 128 == 0 && ql % 16 == 0,
+                     "engine: int4 weights need hidden and inter in multiples of 128 (and q rows of 16)");
+    } else {
+        const int epl = 16 / (int)wsz;
+        LLMI_REQUIRE(c.hidden % epl == 0 && ql % epl == 0 && il % epl == 0,
+                     "engine: hidden, q rows per rank and inter per rank must be multiples of 16 bytes");
+    }
 
     LLMI_HIP(hipSetDevice(device));
     LLMI_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
@@ -105,15 +115,15 @@ int Engine::alloc_weights() {
     const size_t qkv_rows = ql + 2 * kvrows;
     for (int l = 0; l < c.layers; ++l) {
         Off& t = lo[l];
-        t.qkv = b.take(qkv_rows * H * wsz);
-        t.o = b.take(H * ql * wsz);
-        t.gu = b.take(2 * il * H * wsz);
-        t.down = b.take(H * il * wsz);
-        if (wdt == LLMI_I8) {
-            t.qs = b.take(qkv_rows * 2);
-            t.os = b.take(H * 2);
-            t.gs = b.take(2 * il * 2);
-            t.ds = b.take(H * 2);
+        t.qkv = b.take(lin_bytes(wdt, qkv_rows, H));
+        t.o = b.take(lin_bytes(odt(), H, ql));
+        t.gu = b.take(lin_bytes(wdt, 2 * il, H));
+        t.down = b.take(lin_bytes(wdt, H, il));
+        if (quantised()) {
+            t.qs = b.take(scale_bytes(wdt, qkv_rows, H));
+            t.os = b.take(scale_bytes(odt(), H, ql));
+            t.gs = b.take(scale_bytes(wdt, 2 * il, H));
+            t.ds = b.take(scale_bytes(wdt, H, il));
         }
         t.an = b.take(H * esz);
         t.fn = b.take(H * esz);
@@ -128,7 +138,7 @@ int Engine::alloc_weights() {
         L.o = wblob + lo[l].o;
         L.gu = wblob + lo[l].gu;
         L.down = wblob + lo[l].down;
-        if (wdt == LLMI_I8) {
+        if (quantised()) {
             L.qkv_s = (__half*)(wblob + lo[l].qs);
             L.o_s = (__half*)(wblob + lo[l].os);
             L.gu_s = (__half*)(wblob + lo[l].gs);
@@ -141,8 +151,10 @@ int Engine::alloc_weights() {
     final_norm = wblob + fnorm;
     embed = wblob + emb;
     // bytes streamed per forward: every linear weight (+scales), norms, lm_head, one embedding row
-    uint64_t per_layer = (qkv_rows * H + H * ql + 2 * il * H + H * il) * wsz + 2 * H * esz;
-    if (wdt == LLMI_I8) per_layer += (qkv_rows + H + 2 * il + H) * 2;
+    // (int4: nibbles and group scales for q/k/v, gate_up and down; W_o int8 with its row scales)
+    const uint64_t per_layer = lin_bytes(wdt, qkv_rows, H) + scale_bytes(wdt, qkv_rows, H) + lin_bytes(odt(), H, ql) +
+                               scale_bytes(odt(), H, ql) + lin_bytes(wdt, 2 * il, H) + scale_bytes(wdt, 2 * il, H) +
+                               lin_bytes(wdt, H, il) + scale_bytes(wdt, H, il) + 2 * H * esz;
     stream_bytes = per_layer * c.layers + (uint64_t)vl * H * esz + H * esz + H * esz;
     return LLMI_OK;
 }
@@ -221,6 +233,7 @@ int Engine::weights_changed() {
 int Engine::load_synthetic(uint64_t sd) {
     LLMI_TRY(weights_changed());
     seed = sd;
+    if (wdt == LLMI_I4) return load_synthetic_i4();
     const int H = c.hidden, r = c.tp_rank;
     const int lin = (wdt == LLMI_I8) ? LLMI_SYN_INT8 : LLMI_SYN_LINEAR;
     auto fill = [&](void* dst, size_t row_off, int kind, int dt, uint32_t tid, int rows, int cols, int row0,
@@ -262,6 +275,54 @@ int Engine::load_synthetic(uint64_t sd) {
     return LLMI_OK;
 }
 
+// int4: the quantisation of the fp16 engine's synthetic model. Every linear tensor is generated
+// as fp32 (the fp16 values) into the staging buffer a block of rows at a time and quantised from
+// there: q/k/v, gate_up and down in 4-bit groups, W_o to W8A16.
+int Engine::load_synthetic_i4() {
+    const int H = c.hidden;
+    auto lin = [&](void* q, __half* sc, size_t row_off, int qdt, uint32_t tid, int rows, int cols) -> int {
+        int chunk = 0;
+        LLMI_TRY(quant_stage((size_t)cols * 4, rows, &chunk));
+        float* rows_dev = reinterpret_cast<float*>(qstage + kQStageHead);
+        for (int r0 = 0; r0 < rows; r0 += chunk) {
+            const int n = std::min(chunk, rows - r0);
+            LLMI_TRY(synth_fill_launch(rows_dev, LLMI_F32, LLMI_SYN_LINEAR, seed, tid, n, cols, r0, 0, cols, stream));
+            LLMI_TRY(quant_rows(rows_dev, (size_t)cols, n, cols, q, sc, row_off + r0, qdt, nullptr));
+        }
+        return LLMI_OK;
+    };
+    auto fill = [&](void* dst, int kind, uint32_t tid, int rows, int cols) -> int {
+        return synth_fill_launch(dst, edt, kind, seed, tid, rows, cols, 0, 0, cols, stream);
+    };
+    qstage_hold = true;
+    int rc = LLMI_OK;
+    for (int l = 0; l < c.layers && rc == LLMI_OK; ++l) {
+        Layer& L = layers[l];
+        auto t = [&](uint32_t k) { return prng::layer_tid(l, k); };
+        auto run = [&]() -> int {
+            LLMI_TRY(lin(L.qkv, L.qkv_s, 0, LLMI_I4, t(prng::Q), ql, H));
+            LLMI_TRY(lin(L.qkv, L.qkv_s, ql, LLMI_I4, t(prng::K), kvrows, H));
+            LLMI_TRY(lin(L.qkv, L.qkv_s, ql + kvrows, LLMI_I4, t(prng::V), kvrows, H));
+            LLMI_TRY(lin(L.o, L.o_s, 0, LLMI_I8, t(prng::O), H, ql));
+            LLMI_TRY(lin(L.gu, L.gu_s, 0, LLMI_I4, t(prng::GATE), il, H));
+            LLMI_TRY(lin(L.gu, L.gu_s, il, LLMI_I4, t(prng::UP), il, H));
+            LLMI_TRY(lin(L.down, L.down_s, 0, LLMI_I4, t(prng::DOWN), H, il));
+            LLMI_TRY(fill(L.attn_norm, LLMI_SYN_GAMMA, t(prng::ATTN_NORM), 1, H));
+            return fill(L.ffn_norm, LLMI_SYN_GAMMA, t(prng::FFN_NORM), 1, H);
+        };
+        rc = run();
+    }
+    if (rc == LLMI_OK) rc = fill(lm_head, LLMI_SYN_LINEAR, prng::LM_HEAD, vl, H);
+    if (rc == LLMI_OK) rc = fill(final_norm, LLMI_SYN_GAMMA, prng::FINAL_NORM, 1, H);
+    if (rc == LLMI_OK) rc = fill(embed, LLMI_SYN_EMBED, prng::EMBED, c.vocab, H);
+    const hipError_t e = hipStreamSynchronize(stream);
+    qstage_hold = false;
+    quant_release();
+    LLMI_TRY(rc);
+    LLMI_HIP(e);
+    return LLMI_OK;
+}
+
 // ------------------------------------------------ weights from the reference's files
 // LlamaWeight<T>::loadWeights / LlamaLayerWeight<T>::loadWeights (llama_weights.cc:41-53,
 // layer_weights.cc:48-66) with loadWeightFromBin<T, float> (weight_utils.cu:90-187): one
@@ -295,28 +356,45 @@ void Engine::quant_release() {
     qstage = nullptr;
     qstage_bytes = 0;
 }
-int Engine::quant_put(const std::string& nm, const float* src, size_t src_ld, size_t row0, int rows, int col0,
-                      int cols, void* q_dst, size_t q_row_off, __half* s_dst) {
-    const size_t row_bytes = src_ld * 4;
+// the staging buffer for blocks of at most *chunk rows of row_bytes each
+int Engine::quant_stage(size_t row_bytes, int rows, int* chunk) {
     LLMI_REQUIRE(row_bytes <= kQStageBytes, "load_tensor: a row exceeds the quantiser's staging buffer");
-    const int chunk = (int)std::min<size_t>((size_t)rows, kQStageBytes / row_bytes);
-    const size_t need = kQStageHead + (size_t)chunk * row_bytes;
+    *chunk = (int)std::min<size_t>((size_t)rows, kQStageBytes / row_bytes);
+    const size_t need = kQStageHead + (size_t)*chunk * row_bytes;
     if (need > qstage_bytes) {
         LLMI_HIP(hipStreamSynchronize(stream));
         quant_release();
         LLMI_HIP(hipMalloc(&qstage, need));
         qstage_bytes = need;
     }
+    return LLMI_OK;
+}
+// n staged fp32 rows [n, ld] -> rows [q_row, q_row + n) of a quantised tensor of dtype qdt:
+// LLMI_I8 the columns [col0, col0 + cols) with one scale a row, LLMI_I4 whole rows (col0 0,
+// cols == ld) in 4-bit groups with cols / 128 scales a row
+int Engine::quant_rows(const float* rows_dev, size_t ld, int n, int cols, void* q_dst, __half* s_dst, size_t q_row,
+                       int qdt, int32_t* bad, int col0) {
+    if (qdt == LLMI_I4) {
+        LLMI_REQUIRE(col0 == 0 && (size_t)cols == ld, "load_tensor: int4 tensors are quantised in whole rows");
+        return quantize_groups_i4_launch(rows_dev, ld, n, cols, static_cast<uint8_t*>(q_dst) + q_row * (size_t)(cols / 2),
+                                         s_dst + q_row * (size_t)(cols / 128), bad, stream);
+    }
+    return quantize_rows_i8_launch(rows_dev, ld, n, (int)ld, col0, cols,
+                                   static_cast<int8_t*>(q_dst) + q_row * (size_t)cols, s_dst + q_row, bad, stream);
+}
+int Engine::quant_put(const std::string& nm, const float* src, size_t src_ld, size_t row0, int rows, int col0,
+                      int cols, void* q_dst, size_t q_row_off, __half* s_dst, int qdt) {
+    const size_t row_bytes = src_ld * 4;
+    int chunk = 0;
+    LLMI_TRY(quant_stage(row_bytes, rows, &chunk));
     int32_t* bad = reinterpret_cast<int32_t*>(qstage);
     float* rows_dev = reinterpret_cast<float*>(qstage + kQStageHead);
     LLMI_HIP(hipMemsetAsync(bad, 0, 4, stream));
-    int8_t* q = static_cast<int8_t*>(q_dst) + q_row_off * (size_t)cols;
     for (int r0 = 0; r0 < rows; r0 += chunk) {
         const int n = std::min(chunk, rows - r0);
         LLMI_HIP(hipMemcpyAsync(rows_dev, src + (row0 + r0) * src_ld, (size_t)n * row_bytes, hipMemcpyHostToDevice,
                                 stream));
-        LLMI_TRY(quantize_rows_i8_launch(rows_dev, src_ld, n, (int)src_ld, col0, cols, q + (size_t)r0 * cols,
-                                         s_dst + q_row_off + r0, bad, stream));
+        LLMI_TRY(quant_rows(rows_dev, src_ld, n, cols, q_dst, s_dst, q_row_off + r0, qdt, bad, col0));
     }
     int32_t nbad = 0;
     LLMI_HIP(hipMemcpyAsync(&nbad, bad, 4, hipMemcpyDeviceToHost, stream));
@@ -330,7 +408,8 @@ int Engine::quant_put(const std::string& nm, const float* src, size_t src_ld, si
 }
 
 // name: the reference's file stem without ".bin" (e.g. "model.layers.3.self_attn.qkv.weight")
-// quantize (int8 engines only): the four linear tensors are quantised to W8A16 on the device
+// quantize (int8 and int4 engines only): the four linear tensors are quantised on the device, to
+// W8A16, or -- int4 engines -- q/k/v, gate_up and down to 4-bit groups and o_proj to W8A16
 int Engine::load_tensor(const char* name, const float* src, size_t count, bool quantize) {
     const int rc = load_tensor_impl(name, src, count, quantize);
     if (!qstage_hold) quant_release();
@@ -339,7 +418,7 @@ int Engine::load_tensor(const char* name, const float* src, size_t count, bool q
 
 int Engine::load_tensor_impl(const char* name, const float* src, size_t count, bool quantize) {
     LLMI_REQUIRE(name && src, "load_tensor: null argument");
-    LLMI_REQUIRE(!quantize || wdt == LLMI_I8, "quantize needs an int8 engine");
+    LLMI_REQUIRE(!quantize || quantised(), "quantize needs an int8 engine (or an int4 one)");
     LLMI_TRY(weights_changed());
     const std::string nm(name);
     const size_t H = c.hidden, D = c.head_dim, QR = (size_t)c.heads * D, KR = (size_t)c.kv_heads * D;
@@ -353,8 +432,8 @@ int Engine::load_tensor_impl(const char* name, const float* src, size_t count, b
         return LLMI_OK;
     };
     auto lin_ok = [&]() -> int {
-        LLMI_REQUIRE(quantize || wdt != LLMI_I8,
-                     "load_tensor: int8 engines take fp32 weights only through the quantised loaders "
+        LLMI_REQUIRE(quantize || !quantised(),
+                     "load_tensor: int8 and int4 engines take fp32 weights only through the quantised loaders "
                      "(llmi_engine_load_bin_quantized / llmi_engine_load_tensor_quantized), or synthetic ones");
         return LLMI_OK;
     };
@@ -387,9 +466,9 @@ int Engine::load_tensor_impl(const char* name, const float* src, size_t count, b
         LLMI_TRY(lin_ok());
         LLMI_TRY(need((QR + 2 * KR) * H));
         if (quantize) {
-            LLMI_TRY(quant_put(nm, src, H, r * ql, ql, 0, (int)H, L.qkv, 0, L.qkv_s));
-            LLMI_TRY(quant_put(nm, src, H, QR + r * kvrows, kvrows, 0, (int)H, L.qkv, ql, L.qkv_s));
-            return quant_put(nm, src, H, QR + KR + r * kvrows, kvrows, 0, (int)H, L.qkv, ql + kvrows, L.qkv_s);
+            LLMI_TRY(quant_put(nm, src, H, r * ql, ql, 0, (int)H, L.qkv, 0, L.qkv_s, wdt));
+            LLMI_TRY(quant_put(nm, src, H, QR + r * kvrows, kvrows, 0, (int)H, L.qkv, ql, L.qkv_s, wdt));
+            return quant_put(nm, src, H, QR + KR + r * kvrows, kvrows, 0, (int)H, L.qkv, ql + kvrows, L.qkv_s, wdt);
         }
         char* d = (char*)L.qkv;
         LLMI_TRY(put_host(d, wdt, src, H, ql, (int)H, r * ql, 0, stream));
@@ -401,15 +480,15 @@ int Engine::load_tensor_impl(const char* name, const float* src, size_t count, b
         LLMI_TRY(lin_ok());
         LLMI_TRY(need(H * QR));
         // column shard: every rank takes its scale from the whole unsharded row
-        if (quantize) return quant_put(nm, src, QR, 0, (int)H, (int)(r * ql), ql, L.o, 0, L.o_s);
+        if (quantize) return quant_put(nm, src, QR, 0, (int)H, (int)(r * ql), ql, L.o, 0, L.o_s, odt());
         return put_host(L.o, wdt, src, QR, (int)H, ql, 0, r * ql, stream);
     }
     if (leaf == "mlp.gate_up_proj.weight") {
         LLMI_TRY(lin_ok());
         LLMI_TRY(need(2 * I * H));
         if (quantize) {
-            LLMI_TRY(quant_put(nm, src, H, r * il, il, 0, (int)H, L.gu, 0, L.gu_s));
-            return quant_put(nm, src, H, I + r * il, il, 0, (int)H, L.gu, il, L.gu_s);
+            LLMI_TRY(quant_put(nm, src, H, r * il, il, 0, (int)H, L.gu, 0, L.gu_s, wdt));
+            return quant_put(nm, src, H, I + r * il, il, 0, (int)H, L.gu, il, L.gu_s, wdt);
         }
         LLMI_TRY(put_host(L.gu, wdt, src, H, il, (int)H, r * il, 0, stream));
         return put_host((char*)L.gu + (size_t)il * H * ws, wdt, src, H, il, (int)H, I + r * il, 0, stream);
@@ -417,7 +496,7 @@ int Engine::load_tensor_impl(const char* name, const float* src, size_t count, b
     if (leaf == "mlp.down_proj.weight") {
         LLMI_TRY(lin_ok());
         LLMI_TRY(need(H * I));
-        if (quantize) return quant_put(nm, src, I, 0, (int)H, (int)(r * il), il, L.down, 0, L.down_s);
+        if (quantize) return quant_put(nm, src, I, 0, (int)H, (int)(r * il), il, L.down, 0, L.down_s, wdt);
         return put_host(L.down, wdt, src, I, (int)H, il, 0, r * il, stream);
     }
     set_last_error("[llmi][ERROR] load_tensor: unknown tensor " + nm);
@@ -426,7 +505,7 @@ int Engine::load_tensor_impl(const char* name, const float* src, size_t count, b
 
 // Llama<T>::loadWeights(weight_path): weight_path + "<name>.bin" for every tensor.
 int Engine::load_bin(const char* weight_path, bool quantize) {
-    LLMI_REQUIRE(!quantize || wdt == LLMI_I8, "quantize needs an int8 engine");
+    LLMI_REQUIRE(!quantize || quantised(), "quantize needs an int8 engine (or an int4 one)");
     qstage_hold = true;  // one staging buffer for all the tensors, released on return
     const int rc = load_bin_impl(weight_path, quantize);
     qstage_hold = false;

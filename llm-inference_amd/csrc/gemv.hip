@@ -1,5 +1,5 @@
 // HBM-streaming GEMV for batch-1 decode: y = W x, W [n_rows, k] row-major
-// (fp16 / fp32 / int8+row-scale), x fp32, fp32 accumulate.
+// (fp16 / fp32 / int8+row-scale / int4+group-scale), x fp32, fp32 accumulate.
 //
 // Replaces launchLinearGemm -> cublasGemmEx with m = 1 (src/kernels/linear.cu:38-104,
 // src/kernels/cublas_utils.cc:32-71) for the q/k/v, o, gate_up, down and lm_head
@@ -29,12 +29,14 @@ namespace gemv_detail {
 #define LLMI_GEMV_MAX_GRID 1024
 #endif
 template <typename WT>
-int launch_epi(const GemvArgs& a, int grid, hipStream_t s);  // gemv_{f16,f32,i8}.hip
+int launch_epi(const GemvArgs& a, int grid, hipStream_t s);  // gemv_{f16,f32,i8,i4}.hip
+template <>
+int launch_epi<i4w>(const GemvArgs& a, int grid, hipStream_t s);
 }  // namespace gemv_detail
 
 namespace {
 using namespace gemv_detail;
-int epl_of(int dt) { return dt == LLMI_F16 ? 8 : dt == LLMI_F32 ? 4 : dt == LLMI_I8 ? 16 : 0; }
+int epl_of(int dt) { return dt == LLMI_F16 ? 8 : dt == LLMI_F32 ? 4 : dt == LLMI_I8 ? 16 : dt == LLMI_I4 ? 32 : 0; }
 
 }  // namespace
 
@@ -53,11 +55,24 @@ namespace {
 // the argument contract of gemv_launch (and of gemv_plan, which launches nothing)
 int gemv_check(const GemvArgs& a) {
     const int epl = epl_of(a.w_dtype);
-    LLMI_REQUIRE(epl > 0, "gemv: weight dtype must be f16, f32 or i8");
+    LLMI_REQUIRE(epl > 0, "gemv: weight dtype must be f16, f32, i8 or i4");
+    if (a.w_dtype == LLMI_I4) {
+        // int4 runs the three forms of a single-rank token step (gemv_i4.hip) and nothing else
+        const bool proj = (a.epi == EPI_STORE || a.epi == EPI_SILU_MUL) && a.x_fixed && a.gamma && a.g_dtype == LLMI_F16;
+        const bool down = a.epi == EPI_ATOMIC && a.x && !a.x_fixed && !a.gamma && a.ksplit == 1;
+        if (!(proj || down) || a.kpar > 1 || a.y_tag || a.xt.buf || (a.ldw != 0 && a.ldw != a.k)) {
+            set_last_error("[llmi][ERROR] gemv: int4 weights run a fixed-point x with an fp16 RMSNorm and the store or "
+                           "silu epilogue, or an fp32 x with the atomic epilogue at ksplit 1; no kpar, granule rows, "
+                           "exchange tail or ldw other than 0 / k");
+            return LLMI_EUNSUPPORTED;
+        }
+        LLMI_REQUIRE(a.k > 0 && a.k % 128 == 0, "gemv: int4 weights need k a positive multiple of the 128-column group");
+    }
     LLMI_REQUIRE(a.k > 0 && a.k % epl == 0, "gemv: k must be a positive multiple of 16 bytes of weights");
     LLMI_REQUIRE((size_t)a.k * 4 <= 150 * 1024, "gemv: k too large for LDS staging");
     LLMI_REQUIRE(a.w && (a.x || a.x_fixed) && (a.y || a.epi == EPI_ATOMIC), "gemv: null pointer");
     LLMI_REQUIRE(a.w_dtype != LLMI_I8 || a.scales, "gemv: int8 weights need per-row scales");
+    LLMI_REQUIRE(a.w_dtype != LLMI_I4 || a.scales, "gemv: int4 weights need per-group scales");
     LLMI_REQUIRE(a.epi != EPI_ADD || a.resid, "gemv: EPI_ADD needs resid");
     LLMI_REQUIRE(a.epi != EPI_ARGMAX || a.partials, "gemv: EPI_ARGMAX needs partials");
     LLMI_REQUIRE(a.epi != EPI_SILU_MUL || (a.pair_off > 0 && a.n_rows == 2 * a.pair_off),
@@ -94,6 +109,7 @@ int gemv_launch(const GemvArgs& a, hipStream_t s) {
         case LLMI_F16: return launch_epi<__half>(a, grid, s);
         case LLMI_F32: return launch_epi<float>(a, grid, s);
         case LLMI_I8: return launch_epi<int8_t>(a, grid, s);
+        case LLMI_I4: return launch_epi<i4w>(a, grid, s);
     }
     return LLMI_EINVAL;
 }

@@ -1,5 +1,7 @@
 // GEMV body of gemv_kernel (gemv_launch.h; design notes in gemv.hip).
 #pragma once
+#include <type_traits>
+
 #include "io.h"
 #include "kernels.h"
 
@@ -27,6 +29,13 @@ template <typename WT> struct WT_ { };
 template <> struct WT_<__half> { static constexpr int EPL = 8; };
 template <> struct WT_<float> { static constexpr int EPL = 4; };
 template <> struct WT_<int8_t> { static constexpr int EPL = 16; };
+// LLMI_I4 (include/llmi.h, llmi_quantize_groups_i4): two nibbles a byte, a 16-B chunk is 32
+// columns, one fp16 scale per 128 columns (4 chunks) of a row in GemvArgs::scales [n_rows][k / 128]
+struct i4w { uint8_t b; };
+template <> struct WT_<i4w> { static constexpr int EPL = 32; };
+template <typename WT> inline constexpr bool kIsI4 = std::is_same<WT, i4w>::value;
+// bytes of n weights
+template <typename WT> __host__ __device__ constexpr size_t w_bytes(size_t n) { return kIsI4<WT> ? n / 2 : n * sizeof(WT); }
 
 __device__ __forceinline__ float dot_packet(const uint4& w, const float4* xp, int nc, __half*) {
     const __half2* h = reinterpret_cast<const __half2*>(&w);
@@ -62,6 +71,43 @@ __device__ __forceinline__ float dot_packet(const uint4& w, const float4* xp, in
         s = fmaf(i8(ws[p], 1), x.y, s);
         s = fmaf(i8(ws[p], 2), x.z, s);
         s = fmaf(i8(ws[p], 3), x.w, s);
+    }
+    return s;
+}
+
+// nibble n decodes to n - 8 (the quantiser writes 1..15; nibble 0 is -8). No integer-to-float
+// convert (quarter rate on the VALU): a nibble OR-ed into the mantissa of fp16 1024 (0x6400) IS
+// 1024 + n, so one packed fp16 op per two weights lands on the exact integer n - 8:
+//   bits 0-3 of each half:  (w & 0x000F000F) | 0x64006400 = 1024 + n     -> - 1032
+//   bits 4-7 of each half:  (w & 0x00F000F0) | 0x64006400 = 1024 + 16 n  -> / 16 - 72
+// and w >> 8 gives the other two nibbles of each half the same way. A dword's low half holds
+// columns 0-3 and its high half columns 4-7, so each half2 pairs column j with column j + 4;
+// the fp16 values go into fp32 FMAs against the fp32 x (fp32 accumulate). The dot is unscaled:
+// the caller multiplies by the group's scale.
+typedef _Float16 i4_h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ i4_h2 nib_lo(uint32_t w) {
+    const i4_h2 v = __builtin_bit_cast(i4_h2, (w & 0x000F000Fu) | 0x64006400u);
+    return v - (i4_h2){(_Float16)1032.0f, (_Float16)1032.0f};
+}
+__device__ __forceinline__ i4_h2 nib_hi(uint32_t w) {
+    const i4_h2 v = __builtin_bit_cast(i4_h2, (w & 0x00F000F0u) | 0x64006400u);
+    return v * (i4_h2){(_Float16)0.0625f, (_Float16)0.0625f} - (i4_h2){(_Float16)72.0f, (_Float16)72.0f};
+}
+__device__ __forceinline__ float dot_packet(const uint4& w, const float4* xp, int nc, i4w*) {
+    const uint32_t ws[4] = {w.x, w.y, w.z, w.w};
+    float s = 0.f;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        const float4 x0 = xp[(2 * p) * nc], x1 = xp[(2 * p + 1) * nc];
+        const i4_h2 c04 = nib_lo(ws[p]), c15 = nib_hi(ws[p]), c26 = nib_lo(ws[p] >> 8), c37 = nib_hi(ws[p] >> 8);
+        s = fmaf((float)c04.x, x0.x, s);
+        s = fmaf((float)c15.x, x0.y, s);
+        s = fmaf((float)c26.x, x0.z, s);
+        s = fmaf((float)c37.x, x0.w, s);
+        s = fmaf((float)c04.y, x1.x, s);
+        s = fmaf((float)c15.y, x1.y, s);
+        s = fmaf((float)c26.y, x1.z, s);
+        s = fmaf((float)c37.y, x1.w, s);
     }
     return s;
 }
@@ -115,6 +161,14 @@ inline int gemv_pick_unroll(int epl, int epi, const GemvArgs& a, int groups) {
     const int kl = (epi == EPI_ATOMIC) ? a.k / a.ksplit : a.k;
     const int nc = kl / epl / (a.kpar > 1 ? a.kpar : 1);  // chunks one wave streams
     auto slots = [&](int u) { const int b = kWave * u; return (nc + b - 1) / b * b; };
+    // int4: a row is k / 2 bytes (7B hidden: 128 chunks, two loads a lane), so the instantiated
+    // unrolls are 2, 3 and 4: the fewest batch slots, the larger unroll on a tie
+    if (epl == 32) {
+        int b4 = 4;
+        for (int u : {3, 2})
+            if (slots(u) < slots(b4)) b4 = u;
+        return b4;
+    }
     // kpar: only U = 4 is instantiated for the K-parted kernel (launch_u), so it is taken
     // whatever the slot count (13B fp16 at kpar 2: 320 chunks a part would pick U = 5 and
     // fail the launch)
@@ -162,8 +216,9 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
     const int n_groups = (EPI == EPI_SILU_MUL) ? a.pair_off : (a.n_rows + ROWS - 1) / ROWS;
     // LLMI_I8_PIPE: bit EPI enables the software-pipelined int8 stream for that epilogue
     // (4 = gate_up only); LLMI_GEMV_PIPE16 the same for fp16 (both off by default)
-    constexpr bool PIPE = (sizeof(WT) == 1 && kUnroll <= 5 && ((LLMI_I8_PIPE >> EPI) & 1))
-                          || (sizeof(WT) == 2 && ((LLMI_GEMV_PIPE16 >> EPI) & 1));
+    constexpr bool I4 = kIsI4<WT>;
+    constexpr bool PIPE = !I4 && ((sizeof(WT) == 1 && kUnroll <= 5 && ((LLMI_I8_PIPE >> EPI) & 1))
+                                  || (sizeof(WT) == 2 && ((LLMI_GEMV_PIPE16 >> EPI) & 1)));  // (never int4)
     // KPT (GemvArgs::kpar, a template argument so the KPT = 1 kernels are unchanged):
     // wave w takes K part w % KP of the workgroup's group slot w / KP
     constexpr bool KPOK = (EPI == EPI_STORE || EPI == EPI_SILU_MUL) && ROWS <= 2 && !PIPE;
@@ -172,8 +227,8 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
     constexpr int gpw = kWavesPerBlock / KP;                  // groups per workgroup
     const int c_lo = KP > 1 ? kq * (nc / KP) : 0;              // this wave's chunks [c_lo, c_hi)
     const int c_hi = KP > 1 ? c_lo + nc / KP : nc;
-    const size_t row_bytes = (size_t)(a.ldw ? a.ldw : a.k) * sizeof(WT);
-    const char* wbase = reinterpret_cast<const char*>(a.w) + (size_t)ks * k * sizeof(WT);
+    const size_t row_bytes = w_bytes<WT>((size_t)(a.ldw ? a.ldw : a.k));
+    const char* wbase = reinterpret_cast<const char*>(a.w) + w_bytes<WT>((size_t)ks * k);
     const float4* x4 = reinterpret_cast<const float4*>(a.x + (size_t)ks * k);
 
     auto rows_of = [&](int g, int* rows) {
@@ -208,6 +263,37 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
             }
         }
     };
+    // int4: the fp16 group scale of every chunk of a batch (raw bits), loaded beside the chunk;
+    // chunk c lies in group c >> 2, so a wave's load touches 16 adjacent scales of the row. An
+    // out-of-range chunk or row gets scale 0: a masked weight word would decode to -8s, not 0.
+    constexpr int SR = I4 ? ROWS : 1, SU = I4 ? kUnroll : 1;
+    auto load_scales = [&](unsigned short (&sv)[SR][SU], const int* rows, int base) {
+        const int ng = a.k >> 7;  // groups per row (S == 1 for int4)
+#pragma unroll
+        for (int u = 0; u < SU; ++u) {
+            const int c = base + u * kWave + lane;
+            const int cc = c < c_hi ? c : c_hi - 1;
+#pragma unroll
+            for (int r = 0; r < SR; ++r) {
+                const int rr = rows[r] < a.n_rows ? rows[r] : a.n_rows - 1;
+                const unsigned short v =
+                    reinterpret_cast<const unsigned short*>(a.scales)[(size_t)rr * ng + (cc >> 2)];
+                sv[r][u] = (c < c_hi && rows[r] < a.n_rows) ? v : (unsigned short)0;
+            }
+        }
+    };
+    auto dot_batch_i4 = [&](const uint4 (&wv)[ROWS][kUnroll], const unsigned short (&sv)[SR][SU], int base,
+                            float* acc) {
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const int c = base + u * kWave + lane;
+            const float4* xp = xs + (c < c_hi ? c : c_hi - 1);
+#pragma unroll
+            for (int r = 0; r < ROWS; ++r)
+                acc[r] = fmaf(__half2float(__ushort_as_half(sv[r < SR ? r : 0][u < SU ? u : 0])),
+                              dot_packet(wv[r][u], xp, nc, (WT*)nullptr), acc[r]);
+        }
+    };
     auto dot_batch = [&](const uint4 (&wv)[ROWS][kUnroll], int base, float* acc) {
 #pragma unroll
         for (int u = 0; u < kUnroll; ++u) {
@@ -225,6 +311,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
     int rows0[ROWS];
     rows_of(g0, rows0);
     uint4 w0[ROWS][kUnroll];
+    unsigned short s0[SR][SU];  // (int4 only)
     float ss = 0.f;
     const bool wb = XFIX && bid == 0 && a.x_out != nullptr;  // one block writes x back
     if constexpr (XPT > 0) {
@@ -244,6 +331,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
             if (NORM) gv[i] = gamma4<GT>(a.gamma, j);
         }
         load_batch(w0, rows0, c_lo);
+        if constexpr (I4) load_scales(s0, rows0, c_lo);
         // RMSNorm (modeling_llama.py:112-117) as gamma*x staged + one scalar rsqrt per
         // dot product in the epilogue: sum_k W[r,k] gamma_k x_k * rstd.
 #pragma unroll
@@ -283,6 +371,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
             xs[(j % PK) * nc + j / PK] = v;
         }
         load_batch(w0, rows0, c_lo);
+        if constexpr (I4) load_scales(s0, rows0, c_lo);
     }
     seed();
     float rstd = 1.f;
@@ -326,7 +415,8 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) {
                 acc[r] = wave_sum(acc[r]) * rstd;
-                if (a.scales != nullptr && rows[r] < a.n_rows) acc[r] *= __half2float(a.scales[rows[r]]);
+                if constexpr (!I4)  // (int4: the group scales went in with the partial dots)
+                    if (a.scales != nullptr && rows[r] < a.n_rows) acc[r] *= __half2float(a.scales[rows[r]]);
             }
         }
         if (EPI == EPI_SILU_MUL) {
@@ -426,11 +516,18 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
         float acc[ROWS];
 #pragma unroll
         for (int r = 0; r < ROWS; ++r) acc[r] = 0.f;
-        dot_batch(w0, c_lo, acc);
+        if constexpr (I4) dot_batch_i4(w0, s0, c_lo, acc);
+        else dot_batch(w0, c_lo, acc);
         for (int base = c_lo + B; base < c_hi; base += B) {
             uint4 wv[ROWS][kUnroll];
             load_batch(wv, rows0, base);
-            dot_batch(wv, base, acc);
+            if constexpr (I4) {
+                unsigned short sv[SR][SU];
+                load_scales(sv, rows0, base);
+                dot_batch_i4(wv, sv, base, acc);
+            } else {
+                dot_batch(wv, base, acc);
+            }
         }
         finish(g0, rows0, acc);
     }
@@ -444,7 +541,13 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
         for (int base = 0; base < nc; base += kWave * kUnroll) {
             uint4 wv[ROWS][kUnroll];
             load_batch(wv, rows, base);
-            dot_batch(wv, base, acc);
+            if constexpr (I4) {
+                unsigned short sv[SR][SU];
+                load_scales(sv, rows, base);
+                dot_batch_i4(wv, sv, base, acc);
+            } else {
+                dot_batch(wv, base, acc);
+            }
         }
         finish(g, rows, acc);
     }

@@ -1,5 +1,5 @@
 // GEMV launchers (templates) shared by the per-weight-dtype translation units
-// gemv_f16.hip / gemv_f32.hip / gemv_i8.hip, which instantiate launch_epi<WT>
+// gemv_f16.hip / gemv_f32.hip / gemv_i8.hip, which instantiate launch_epi<WT> (gemv_i4.hip specialises it)
 // (split so the build compiles the dtypes in parallel).
 #pragma once
 #include "gemv_impl.h"
@@ -23,7 +23,15 @@ namespace gemv_detail {
 // box, alternating libraries: 3,133 -> 3,115 us, profiles/r07i_int8_minwaves_ab.jsonl)
 #define LLMI_GEMV_MIN_WAVES_I8 4
 #endif
+#ifndef LLMI_GEMV_MIN_WAVES_I4
+// int4: a chunk is dotted against 8 float4 packets of x (32 VGPRs, shared by the wave's two rows),
+// and hipcc hoists the packets of a whole batch: the kernels use 105-140 VGPRs (hipcc remarks;
+// DESIGN.md §3, W4A16), so they get the 256-VGPR budget of 2 waves per SIMD instead of spilling
+// under int8's cap of 128
+#define LLMI_GEMV_MIN_WAVES_I4 2
+#endif
 template <typename WT, int U> constexpr int min_waves() {
+    if (kIsI4<WT>) return LLMI_GEMV_MIN_WAVES_I4;
     return sizeof(WT) == 1 && U <= 5 ? LLMI_GEMV_MIN_WAVES_I8 : LLMI_GEMV_MIN_WAVES;
 }
 

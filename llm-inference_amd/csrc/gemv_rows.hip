@@ -65,6 +65,7 @@ int rows_launch_some(const GemvRowsArgs& p, int i0, int n, hipStream_t s) {
 int gemv_rows_launch(const GemvRowsArgs& p, hipStream_t s) {
     LLMI_REQUIRE(p.m >= 2 && p.m <= kGemvRowsMax, "gemv_rows: m must be 2..8");
     const GemvArgs& a = p.a;
+    if (a.w_dtype == LLMI_I4) return rows_unsupported("int4 weights are a single-row form");
     if (a.kpar > 1) return rows_unsupported("kpar > 1 is a single-row form");
     if (a.y_tag != nullptr) return rows_unsupported("granule rows are a single-row form");
     if (a.xt.buf != nullptr) return rows_unsupported("a fused exchange tail is a single-row form");

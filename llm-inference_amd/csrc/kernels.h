@@ -39,7 +39,7 @@ struct XchgArgs {
 struct GemvArgs {
     unsigned long long* stamps = nullptr;  // debug timeline (WgStamp), null = off
     const void* w = nullptr;       // [n_rows, k] row-major, dtype w_dtype
-    const __half* scales = nullptr;  // int8: per-row fp16 scale
+    const __half* scales = nullptr;  // int8: per-row fp16 scale; int4: [n_rows][k / 128] group scales
     int w_dtype = LLMI_F16;
     int n_rows = 0;                // rows of W
     int k = 0;
@@ -569,5 +569,9 @@ int synth_fill_host(void* out, int out_dtype, int kind, uint64_t seed, uint32_t 
 // scale per row from the whole row's maximum; *bad_rows += rows holding a NaN / infinity
 int quantize_rows_i8_launch(const float* w, size_t ld, int rows, int row_len, int col0, int cols, int8_t* q,
                             __half* scales, int32_t* bad_rows, hipStream_t s);
+// W4A16 (the format: include/llmi.h, llmi_quantize_groups_i4): whole rows of row_len columns,
+// row_len % 128 == 0 -> nibbles q [rows, row_len / 2] and fp16 scales [rows][row_len / 128]
+int quantize_groups_i4_launch(const float* w, size_t ld, int rows, int row_len, uint8_t* q, __half* scales,
+                              int32_t* bad_rows, hipStream_t s);
 
 }  // namespace llmi

@@ -15,7 +15,7 @@ REPO = os.path.dirname(PKG)
 LIB_PATH = os.environ.get("LLMI_LIB_PATH") or os.path.join(PKG, "lib", "libllmi.so")
 HEADER = os.path.join(REPO, "include", "llmi.h")
 
-F32, F16, I8, I32, I64 = 0, 1, 2, 3, 4
+F32, F16, I8, I32, I64, I4 = 0, 1, 2, 3, 4, 5
 SYN_LINEAR, SYN_EMBED, SYN_GAMMA, SYN_INT8, SYN_INT8_SCALE = 0, 1, 2, 3, 4
 
 
@@ -130,6 +130,7 @@ _SIGS = {
     "llmi_synth_fill_host": (_I, [_P, _I, _I, _U64, _U32, _I, _I, _I, _I, _I]),
     "llmi_synth_prompt": (_I, [_U64, _I, _I, _P]),
     "llmi_quantize_rows_i8": (_I, [_P, _SZ, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "llmi_quantize_groups_i4": (_I, [_P, _SZ, _I, _I, _P, _P, _P, _P]),
     "llmi_device_alloc": (_I, [C.POINTER(_P), _SZ]),
     "llmi_device_memset": (_I, [_P, _I, _SZ]),
     "llmi_device_memset_async": (_I, [_P, _I, _SZ, _P]),

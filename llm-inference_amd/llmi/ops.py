@@ -257,6 +257,28 @@ def quantizeRowsInt8(w: torch.Tensor, col0: int = 0, cols: int = None, row_len: 
     return q, scales
 
 
+def quantizeGroupsInt4(w: torch.Tensor):
+    """W4A16 quantiser (llmi_quantize_groups_i4): w fp32 [rows, k], k a multiple of 128 ->
+    (q uint8 [rows, k / 2]: nibble q + 8, the low nibble the even column; scales fp16
+    [rows, k / 128]: one per group of 128 columns) with w ~= q * s. Raises LlmiError when a row
+    holds a NaN or an infinity (the error's bad_rows attribute is the kernel's count of such rows)."""
+    _dev(w)
+    if w.dtype != torch.float32 or w.dim() != 2 or not w.is_contiguous():
+        raise ValueError("quantizeGroupsInt4: w must be a contiguous fp32 [rows, k] tensor")
+    rows, k = w.shape
+    q = torch.empty(rows, k // 2, device=w.device, dtype=torch.uint8)
+    scales = torch.empty(rows, k // 128, device=w.device, dtype=torch.float16)
+    bad = torch.zeros(1, device=w.device, dtype=torch.int32)
+    call("llmi_quantize_groups_i4", w.data_ptr(), k, rows, k, q.data_ptr(), scales.data_ptr(), bad.data_ptr(),
+         _stream())
+    n_bad = int(bad.item())
+    if n_bad:
+        err = _lib.LlmiError(f"quantizeGroupsInt4: {n_bad} row(s) hold a NaN or an infinity")
+        err.bad_rows = n_bad
+        raise err
+    return q, scales
+
+
 # ---------------------------------------------- context-phase (prefill) operators
 def _i32(t):
     return t.to(torch.int32).contiguous()
