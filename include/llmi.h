@@ -253,6 +253,8 @@ typedef struct llmi_debug_attn_oproj_args {
     const void* scales;
     int w_dtype, head_major, n_rows, ldw;
     int* err;
+    void* k_scale; /* cache_dtype LLMI_I8 (KV8): the layer's fp16 row scales [kv_heads, max_seq]; */
+    void* v_scale; /* NULL: unused (an f16 / f32 cache) */
 } llmi_debug_attn_oproj_args;
 int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t stream);
 
@@ -299,6 +301,8 @@ typedef struct llmi_debug_prefill_attn_args {
     float* split_ws;
     size_t split_ws_floats;
     int chunk_blocks;
+    void* k_scale; /* cache_dtype LLMI_I8 (KV8, the scalar kernel only): the layer's fp16 row scales */
+    void* v_scale; /* [kv_heads, max_seq]; NULL: unused (an f16 / f32 cache) */
 } llmi_debug_prefill_attn_args;
 int llmi_debug_prefill_attn(const llmi_debug_prefill_attn_args* args, llmi_stream_t stream);
 int llmi_debug_prefill_attn_plan(const llmi_debug_prefill_attn_args* args, int* cb, int* maxc, int* grid,
@@ -349,6 +353,26 @@ size_t llmi_attn_workspace_bytes(int heads, int head_dim, int max_seq);
 int llmi_attn_decode(const float* qkv, void* k_cache, void* v_cache, int cache_dtype, int layer,
                      int max_seq, int pos, int heads, int kv_heads, int head_dim, int rope,
                      float rope_base, float* out, void* workspace, llmi_stream_t stream);
+
+/* KV8: the int8 KV cache (no reference counterpart; cache_dtype / kv_dtype LLMI_I8).
+ * A cached row x[128] in fp32 (K after RoPE, V as produced) is stored as 128 two's-complement
+ * int8 and ONE fp16 scale, by the W8A16 rule of llmi_quantize_rows_i8 on the row:
+ *   amax = max |x_i|
+ *   s    = fp16_rne(amax / 127); an fp16 zero becomes bits 0x0001 (2^-24), an infinity 0x7BFF (65504)
+ *   q_i  = clamp(rint(x_i / float(s)), -127, 127)
+ * with the correctly rounded fp32 divisions and rint round-half-even. A row holding a NaN or an
+ * infinity stores scale bits 0x7E00 (NaN) and q = 0, so attention over it yields NaN as it does
+ * with an fp16 cache. A cached value is float(q) * float(s), exact in fp32.
+ * Storage: k_cache / v_cache [layers, kv_heads, max_seq, 128] int8 (8-byte aligned);
+ * k_scale / v_scale [layers, kv_heads, max_seq] fp16. Quantisation is fused into the cache write
+ * (the decode attention and the prefill's rope + cache write), dequantisation into the
+ * attention's dot products: score_j = s_k[j] * sum_i q_i k8[j][i], o = sum_j (p_j s_v[j]) v8[j].
+ * llmi_attn_decode_q8 is llmi_attn_decode over such a cache: cache_dtype must be LLMI_I8, the
+ * scale of slot `pos` is written beside its row. */
+int llmi_attn_decode_q8(const float* qkv, void* k_cache, void* v_cache, int cache_dtype, int layer,
+                        int max_seq, int pos, int heads, int kv_heads, int head_dim, int rope,
+                        float rope_base, float* out, void* workspace, llmi_stream_t stream, void* k_scale,
+                        void* v_scale);
 
 /* launchTopKforBeamSearch + launchSampling (src/kernels/topK.h:51-56,
  * sampling.h:12-18) as wired by Llama<T> (K = beamwidth = 1, llama.cpp:59):
@@ -615,7 +639,11 @@ typedef struct llmi_config {
                        * tp_world 1, hidden and inter multiples of 128; decode steps only: prefill,
                        * the ring layer, llmi_batch_create and llmi_group_create return
                        * LLMI_EUNSUPPORTED) */
-    int kv_dtype;     /* LLMI_F16 (throughput) or LLMI_F32 (parity) */
+    int kv_dtype;     /* LLMI_F16 (throughput), LLMI_F32 (parity) or LLMI_I8 (KV8: int8 rows with one
+                       * fp16 scale per (layer, kv head, position) -- the format: llmi_attn_decode_q8;
+                       * any weight dtype; half the fp16 cache's bytes + 1.6 %. The fused q/k/v +
+                       * attention launch is not taken, and prefill runs the scalar attention the
+                       * fp32 cache runs: the MFMA attention and exact = 0 / fp8-lo modes need fp16) */
     int tp_rank, tp_world;
 } llmi_config;
 
@@ -757,9 +785,14 @@ int llmi_engine_tokens(llmi_engine* e, int32_t* out, int n, int* n_valid);
 int llmi_engine_logits(llmi_engine* e, float* out, int n);
 /* fp32 residual stream (hidden) after the last forward. */
 int llmi_engine_hidden(llmi_engine* e, float* out, int n);
-/* Read one cache slot (layer, pos) of K or V as fp32 [kv_heads_local, head_dim]. */
+/* Read one cache slot (layer, pos) of K or V as fp32 [kv_heads_local, head_dim] (an int8
+ * cache: the dequantised q * s). */
 int llmi_engine_kv_slot(llmi_engine* e, int layer, int pos, int which_v, float* out);
-/* Bytes of weights (and KV per position) one forward streams on this rank. */
+/* An int8 cache's slot as stored: q [kv_heads_local, head_dim] int8 and the rows' fp16 scale
+ * bits [kv_heads_local]. LLMI_EINVAL on an f16 / f32 cache. */
+int llmi_engine_kv_slot_q8(llmi_engine* e, int layer, int pos, int which_v, int8_t* q, uint16_t* scale_bits);
+/* Bytes of weights (and KV per position: K and V rows, with an int8 cache their scales too --
+ * layers * kv_heads * (128 + 2) * 2) one forward streams on this rank. */
 int llmi_engine_bytes(llmi_engine* e, uint64_t* weight_bytes, uint64_t* kv_bytes_per_pos);
 /* hipStream_t the engine launches on. */
 llmi_stream_t llmi_engine_stream(llmi_engine* e);

@@ -183,8 +183,18 @@ int attn_decode_launch(const AttnArgs& a, hipStream_t s) {
             hipLaunchKernelGGL((attn_decode_kernel<float, true>), grid, dim3(kThreads), kAttnLds, s, a, ns);
         else
             hipLaunchKernelGGL((attn_decode_kernel<float, false>), grid, dim3(kThreads), kAttnLds, s, a, ns);
+    } else if (a.cache_dtype == LLMI_I8) {
+        LLMI_REQUIRE(a.k_scale && a.v_scale, "attn: an int8 cache needs its row scales (k_scale, v_scale)");
+        LLMI_REQUIRE((uintptr_t)a.k_cache % 8 == 0 && (uintptr_t)a.v_cache % 8 == 0 && (uintptr_t)a.k_scale % 2 == 0 &&
+                         (uintptr_t)a.v_scale % 2 == 0,
+                     "attn: an int8 cache must be 8-byte aligned, its scales 2-byte");
+        LLMI_REQUIRE(!a.qkv_tag, "attn: the fused q/k/v launch takes no int8 cache");
+        if (hs)
+            hipLaunchKernelGGL((attn_decode_kernel<int8_t, true>), grid, dim3(kThreads), kAttnLds, s, a, ns);
+        else
+            hipLaunchKernelGGL((attn_decode_kernel<int8_t, false>), grid, dim3(kThreads), kAttnLds, s, a, ns);
     } else {
-        LLMI_REQUIRE(false, "attn: cache dtype must be f16 or f32");
+        LLMI_REQUIRE(false, "attn: cache dtype must be f16, f32 or i8");
     }
     LLMI_HIP(hipGetLastError());
     if (a.direct_out) {

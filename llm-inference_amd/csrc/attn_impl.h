@@ -34,8 +34,11 @@ __device__ __forceinline__ float block_max(float v, float* red) {
     return t;
 }
 
-// 8 cache elements of one row, as loaded (16 B for fp16, 32 B for fp32)
+// 8 cache elements of one row, as loaded (16 B for fp16, 32 B for fp32, 8 B for int8)
 template <typename KT> struct Raw { uint4 v[sizeof(KT) / 2]; };
+template <> struct Raw<int8_t> { uint32_t v[2]; };
+// int8 cache (KV8, include/llmi.h): a row is 128 int8 and one fp16 scale, value = q * s
+template <typename KT> constexpr bool kQ8 = sizeof(KT) == 1;
 // K/V cache rows: non-temporal loads -- the cache (up to 1 GB at ctx 2048) is streamed once
 // per token and never fits the Infinity Cache. A/B on the 8-layer 7B loop (tools/ab_variants.sh,
 // profiles/r03m_attn_nt_ab.jsonl): 2-5 us per 8-layer token lower in 4 of 4 alternating pairs
@@ -50,6 +53,25 @@ __device__ __forceinline__ Raw<float> ld_raw(const float* p) {
     r.v[0] = ld_nt16(p);
     r.v[1] = ld_nt16(p + 4);
     return r;
+}
+// int8 rows keep the 16-lanes-per-row map with one 8-byte load per lane (as ld_w8 for an int8 W_o)
+__device__ __forceinline__ Raw<int8_t> ld_raw(const int8_t* p) {
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 u = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+    Raw<int8_t> r;
+    r.v[0] = u.x;
+    r.v[1] = u.y;
+    return r;
+}
+// the 8 integers q (unscaled). Written as biased unsigned bytes (^ 0x80, convert, - 128: exact in
+// fp32) to invite the byte-select conversions; the compiler folds it back to a sign extension and
+// v_cvt_f32_i32 per element (64 a lane for the block's 8 rows), the plain form's instructions
+__device__ __forceinline__ void unpack8(const Raw<int8_t>& r, float* v) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const uint32_t u = r.v[i / 4] ^ 0x80808080u;
+        v[i] = (float)((u >> (8 * (i % 4))) & 0xffu) - 128.f;
+    }
 }
 __device__ __forceinline__ void unpack8(const Raw<__half>& r, float* v) {
     const __half2* h = reinterpret_cast<const __half2*>(&r.v[0]);
@@ -76,6 +98,47 @@ __device__ __forceinline__ void store_cache(float* p, float v) { *p = v; }
 template <typename KT> __device__ __forceinline__ float cache_round(float v);
 template <> __device__ __forceinline__ float cache_round<__half>(float v) { return __half2float(__float2half(v)); }
 template <> __device__ __forceinline__ float cache_round<float>(float v) { return v; }
+// int8 cache: the row is rounded as a whole once its maximum is known (q8_round_row)
+template <> __device__ __forceinline__ float cache_round<int8_t>(float v) { return v; }
+
+// KV8 row rule (include/llmi.h; quant.hip's W8A16 rule on the 128-element row). |x| as unsigned
+// bits orders like the magnitudes with every infinity and NaN at or above 0x7F800000, so the
+// integer maximum finds amax and the non-finite rows (fmaxf would drop a NaN).
+__device__ __forceinline__ uint32_t q8_abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
+__device__ __forceinline__ unsigned short q8_scale_bits(uint32_t amax_bits) {
+    if (amax_bits >= 0x7F800000u) return 0x7E00;  // a NaN / infinity in the row: NaN scale, q = 0
+    unsigned short sb = __half_as_ushort(__float2half_rn(__fdiv_rn(__uint_as_float(amax_bits), 127.0f)));
+    if (sb == 0) sb = 1;                  // below half the smallest subnormal: 2^-24
+    else if (sb == 0x7C00) sb = 0x7BFF;   // past the fp16 range: 65504
+    return sb;
+}
+// the integer q as a float (0 in a non-finite row)
+__device__ __forceinline__ float q8_quant(float x, unsigned short sb) {
+    if (sb == 0x7E00) return 0.f;
+    return fminf(fmaxf(rintf(__fdiv_rn(x, __half2float(__ushort_as_half(sb)))), -127.f), 127.f);
+}
+// One wave quantises the 128-element row in LDS (lane: elements 2 lane, 2 lane + 1): the row
+// maximum through the wave butterfly, the integers written back to LDS as floats (the current
+// position then goes through the same q, scale arithmetic as a row read back from the cache),
+// and -- write -- two bytes per lane (128 contiguous bytes a wave) and the scale to the cache.
+// Returns the scale's bits.
+__device__ __forceinline__ unsigned short q8_round_row(float* row_s, bool write, int8_t* dst, __half* sdst) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const float x0 = row_s[2 * lane], x1 = row_s[2 * lane + 1];
+    uint32_t m = max(q8_abs_bits(x0), q8_abs_bits(x1));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    const unsigned short sb = q8_scale_bits(m);
+    const float q0 = q8_quant(x0, sb), q1 = q8_quant(x1, sb);
+    row_s[2 * lane] = q0;
+    row_s[2 * lane + 1] = q1;
+    if (write) {
+        const unsigned short pk = (unsigned short)(((uint32_t)(int)q0 & 0xFFu) | (((uint32_t)(int)q1 & 0xFFu) << 8));
+        reinterpret_cast<unsigned short*>(dst)[lane] = pk;
+        if (lane == 0) *sdst = __ushort_as_half(sb);
+    }
+    return sb;
+}
 
 // HF rotary angle (modeling_llama.py:130-141): inv_freq = 1 / fp32(base^(2i/d)) with
 // the power correctly rounded (== torch's fp32 pow), angle = fp32(pos * inv_freq),
@@ -169,6 +232,7 @@ template <typename KT, typename IO, bool HOST_SIZED = false, bool TAGGED = false
 __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, int ns, float* smem,
                                           const WgStamp* ts = nullptr) {
     static_assert(!TAGGED || HOST_SIZED, "the fused launch sizes the attention grid on the host");
+    static_assert(!TAGGED || !kQ8<KT>, "the fused q/k/v launch takes no int8 cache (qkv_attn_supported)");
     float* q_s = smem;
     float* kcur_s = q_s + D;
     float* vcur_s = kcur_s + D;
@@ -188,6 +252,17 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, i
     const float* vrow = a.qkv + (size_t)(a.heads + a.kv_heads + kvh) * D;
     const int seed_per = (a.hidden + a.heads - 1) / a.heads;  // residual slice split 0 seeds
     Raw<KT> kr[NPG], vr[NPG];
+    // int8 cache: the rows' fp16 scales [kv_heads, max_seq], loaded beside the rows (same clamped
+    // index, same issue point, every lane of a 16-lane group the same address)
+    __half* ksc = nullptr;
+    __half* vsc = nullptr;
+    __half ksr[NPG], vsr[NPG];
+    if constexpr (kQ8<KT>) {
+        ksc = a.k_scale + (size_t)kvh * a.max_seq;
+        vsc = a.v_scale + (size_t)kvh * a.max_seq;
+    }
+    (void)ksr;
+    (void)vsr;
     // HOST_SIZED prologue: every load that does not need the position goes out before
     // anything waits (vmcnt retires in issue order, so the position is issued first --
     // the RoPE table read depends on it): K/V rows, the q row, the current k/v rows,
@@ -220,6 +295,10 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, i
             const int jj = j < a.max_seq ? j : start;
             kr[t] = ld_raw(kc + (size_t)jj * D + l16 * 8);
             vr[t] = ld_raw(vc + (size_t)jj * D + l16 * 8);
+            if constexpr (kQ8<KT>) {
+                ksr[t] = ksc[jj];
+                vsr[t] = vsc[jj];
+            }
         }
         const int i = tid & (D / 2 - 1);
         if constexpr (TAGGED) {
@@ -283,6 +362,10 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, i
             const int jj = (j < end && j != pos) ? j : start;
             kr[t] = ld_raw(kc + (size_t)jj * D + l16 * 8);
             vr[t] = ld_raw(vc + (size_t)jj * D + l16 * 8);
+            if constexpr (kQ8<KT>) {
+                ksr[t] = ksc[jj];
+                vsr[t] = vsc[jj];
+            }
         }
     }
 
@@ -355,10 +438,29 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, i
     }
     if (ts) ts->mark(1);  // timeline: q rotated, this split's K/V rows in registers
 
+    // scales of the current position's rows (int8 cache; kcur_s / vcur_s then hold the integers)
+    float kcur_sc = 1.f, vcur_sc = 1.f;
+    if constexpr (kQ8<KT>) {
+        if (owns_pos) {  // uniform over the workgroup
+            // wave 0 rounds the rotated k row, wave 1 the v row; the kv head's first query head
+            // writes the bytes and the scales at slot pos
+            if (tid < 2 * kWave) {
+                const bool isv = tid >= kWave;
+                const unsigned short sb =
+                    q8_round_row(isv ? vcur_s : kcur_s, (h % group) == 0, (isv ? vc : kc) + (size_t)pos * D,
+                                 (isv ? vsc : ksc) + pos);
+                if ((tid & (kWave - 1)) == 0) ml_s[2 + (isv ? 1 : 0)] = __half2float(__ushort_as_half(sb));
+            }
+            __syncthreads();
+            kcur_sc = ml_s[2];
+            vcur_sc = ml_s[3];
+        }
+    } else {
     if (owns_pos && (h % group) == 0 && tid < D) {
         // KV-cache write at slot pos (concat: fused_decoder_self_attention.cu:187-193,292-295)
         store_cache(kc + (size_t)pos * D + tid, kcur_s[tid]);
         store_cache(vc + (size_t)pos * D + tid, vcur_s[tid]);
+    }
     }
     // The current position is always taken from LDS, never re-read from the cache,
     // so no other workgroup depends on the store above within this launch.
@@ -382,6 +484,9 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, i
 #pragma unroll
         for (int i = 0; i < 8; ++i) d = fmaf(qv[i], kv[i], d);
         d = row16_sum(d);  // LPR = 16: the group's lanes are one DPP row
+        // int8: the row's scale after the integer sum (a select, so a stale row's NaN scale --
+        // the slot at pos before this launch, rows past the context -- never reaches a kept score)
+        if constexpr (kQ8<KT>) d *= (j == pos) ? kcur_sc : __half2float(ksr[t]);
         if (l16 == 0 && j < end) p_s[j - start] = d;
     }
     __syncthreads();
@@ -413,7 +518,8 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, i
         } else {
             unpack8(vr[t], vv);
         }
-        const float p = p_s[j - start];
+        float p = p_s[j - start];
+        if constexpr (kQ8<KT>) p *= (j == pos) ? vcur_sc : __half2float(vsr[t]);  // s_v folded into p
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[i] = fmaf(p, vv[i], acc[i]);
     }

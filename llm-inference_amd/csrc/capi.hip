@@ -188,6 +188,7 @@ int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t 
     at.xacc = d.xacc; at.resid = d.resid; at.resid_fixed = d.resid_fixed; at.resid_scale = d.resid_scale;
     at.hidden = d.n_rows;
     at.err = d.err;
+    at.k_scale = static_cast<__half*>(d.k_scale); at.v_scale = static_cast<__half*>(d.v_scale);
     OprojArgs o;
     o.w = d.w; o.scales = reinterpret_cast<const __half*>(d.scales); o.w_dtype = d.w_dtype;
     o.head_major = d.head_major; o.n_rows = d.n_rows; o.ldw = d.ldw;
@@ -217,6 +218,7 @@ PrefillAttnArgs debug_prefill_attn_args(const llmi_debug_prefill_attn_args& d) {
     a.out_hi = static_cast<_Float16*>(d.out_hi); a.out_lo = static_cast<_Float16*>(d.out_lo);
     a.out_lo8 = d.out_lo8; a.split_ws = d.split_ws; a.split_ws_floats = d.split_ws_floats;
     a.chunk_blocks = d.chunk_blocks;
+    a.k_scale = static_cast<__half*>(d.k_scale); a.v_scale = static_cast<__half*>(d.v_scale);
     return a;
 }
 }  // namespace
@@ -397,6 +399,32 @@ int llmi_attn_decode(const float* qkv, void* k_cache, void* v_cache, int cache_d
     a.qkv = qkv;
     a.k_cache = (char*)k_cache + off;
     a.v_cache = (char*)v_cache + off;
+    a.cache_dtype = cache_dtype;
+    a.max_seq = max_seq;
+    a.pos_host = pos;
+    a.heads = heads;
+    a.kv_heads = kv_heads;
+    a.head_dim = head_dim;
+    a.rope = rope;
+    a.rope_base = rope_base;
+    a.out = out;
+    a.workspace = workspace;
+    return attn_decode_launch(a, STREAM(stream));
+}
+
+int llmi_attn_decode_q8(const float* qkv, void* k_cache, void* v_cache, int cache_dtype, int layer, int max_seq,
+                        int pos, int heads, int kv_heads, int head_dim, int rope, float rope_base, float* out,
+                        void* workspace, llmi_stream_t stream, void* k_scale, void* v_scale) {
+    LLMI_REQUIRE(layer >= 0 && kv_heads > 0 && max_seq > 0, "attn_q8: layer, kv_heads and max_seq must be positive");
+    LLMI_REQUIRE(cache_dtype == LLMI_I8, "attn_q8: cache dtype must be i8");
+    LLMI_REQUIRE(k_scale && v_scale, "attn_q8: null scales");
+    AttnArgs a;
+    const size_t rows = (size_t)layer * kv_heads * max_seq;  // cached rows ahead of this layer
+    a.qkv = qkv;
+    a.k_cache = (char*)k_cache + rows * head_dim;
+    a.v_cache = (char*)v_cache + rows * head_dim;
+    a.k_scale = static_cast<__half*>(k_scale) + rows;
+    a.v_scale = static_cast<__half*>(v_scale) + rows;
     a.cache_dtype = cache_dtype;
     a.max_seq = max_seq;
     a.pos_host = pos;

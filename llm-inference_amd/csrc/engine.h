@@ -166,6 +166,18 @@ struct Engine {
     // ----------------------------------------------------------------- KV
     void *kcache = nullptr, *vcache = nullptr;
     size_t kv_layer_elems = 0;
+    // int8 cache (KV8, include/llmi.h): one fp16 scale per cached row [layers, kv_heads, max_seq],
+    // carved from the same allocation after the bytes (256-byte aligned); null otherwise
+    __half *kscale = nullptr, *vscale = nullptr;
+    static size_t kv_align(size_t n) { return (n + 255) & ~(size_t)255; }
+    size_t kv_data_bytes() const { return (size_t)c.layers * kv_layer_elems * dtype_size(c.kv_dtype); }
+    size_t kv_scale_bytes() const { return c.kv_dtype == LLMI_I8 ? (size_t)c.layers * kvl * c.max_seq * 2 : 0; }
+    // one allocation (K or V): the rows, then the scales
+    size_t kv_alloc_bytes() const { return kv_scale_bytes() ? kv_align(kv_data_bytes()) + kv_scale_bytes() : kv_data_bytes(); }
+    __half* kv_scale_layer(int l, int which_v) const {
+        __half* b = which_v ? vscale : kscale;
+        return b ? b + (size_t)l * kvl * c.max_seq : nullptr;
+    }
     // layer l's K (or V) cache [kv_heads, max_seq, head_dim]
     char* kv_layer(int l, int which_v) const {
         return (char*)(which_v ? vcache : kcache) + (size_t)l * kv_layer_elems * dtype_size(c.kv_dtype);

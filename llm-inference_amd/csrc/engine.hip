@@ -64,6 +64,8 @@ AttnArgs Engine::attn_args(int l) const {
     a.k_cache = kv_layer(l, 0);
     a.v_cache = kv_layer(l, 1);
     a.cache_dtype = c.kv_dtype;
+    a.k_scale = kv_scale_layer(l, 0);
+    a.v_scale = kv_scale_layer(l, 1);
     a.max_seq = c.max_seq;
     a.pos_dev = &st->cur_pos;
     a.heads = hl; a.kv_heads = kvl; a.head_dim = c.head_dim;

@@ -223,13 +223,36 @@ int llmi_engine_kv_slot(llmi_engine* e, int layer, int pos, int which_v, float* 
     for (int h = 0; h < g.kvl; ++h) {
         LLMI_HIP(hipMemcpy(tmp.data(), base + ((size_t)h * g.c.max_seq + pos) * D * eb, D * eb,
                            hipMemcpyDeviceToHost));
+        float sc = 0.f;
+        if (g.c.kv_dtype == LLMI_I8) {  // the cached value: q * s (exact in fp32)
+            uint16_t sb = 0;
+            LLMI_HIP(hipMemcpy(&sb, g.kv_scale_layer(layer, which_v) + (size_t)h * g.c.max_seq + pos, 2,
+                               hipMemcpyDeviceToHost));
+            sc = h2f(sb);
+        }
         for (size_t d = 0; d < D; ++d) {
             if (g.c.kv_dtype == LLMI_F32)
                 std::memcpy(out + h * D + d, tmp.data() + d * 4, 4);
+            else if (g.c.kv_dtype == LLMI_I8)
+                out[h * D + d] = (float)(int8_t)tmp[d] * sc;
             else
                 out[h * D + d] = h2f(*reinterpret_cast<uint16_t*>(tmp.data() + d * 2));
         }
     }
+    return LLMI_OK;
+}
+
+int llmi_engine_kv_slot_q8(llmi_engine* e, int layer, int pos, int which_v, int8_t* q, uint16_t* scale_bits) {
+    LLMI_REQUIRE(e && q && scale_bits, "kv_slot_q8: null argument");
+    Engine& g = e->e;
+    LLMI_REQUIRE(g.c.kv_dtype == LLMI_I8, "kv_slot_q8: the engine's KV cache is not int8");
+    LLMI_REQUIRE(layer >= 0 && layer < g.c.layers && pos >= 0 && pos < g.c.max_seq, "kv_slot_q8: out of range");
+    LLMI_HIP(hipStreamSynchronize(g.stream));
+    const size_t D = g.c.head_dim;
+    LLMI_HIP(hipMemcpy2D(q, D, g.kv_layer(layer, which_v) + (size_t)pos * D, (size_t)g.c.max_seq * D, D, g.kvl,
+                         hipMemcpyDeviceToHost));
+    LLMI_HIP(hipMemcpy2D(scale_bits, 2, g.kv_scale_layer(layer, which_v) + pos, (size_t)g.c.max_seq * 2, 2, g.kvl,
+                         hipMemcpyDeviceToHost));
     return LLMI_OK;
 }
 
@@ -238,7 +261,8 @@ int llmi_engine_bytes(llmi_engine* e, uint64_t* weight_bytes, uint64_t* kv_bytes
     const Engine& g = e->e;
     if (weight_bytes) *weight_bytes = g.stream_bytes;
     if (kv_bytes_per_pos)
-        *kv_bytes_per_pos = (uint64_t)g.c.layers * g.kvl * g.c.head_dim * 2 * llmi::dtype_size(g.c.kv_dtype);
+        *kv_bytes_per_pos = (uint64_t)g.c.layers * g.kvl * 2 *  // (int8 rows carry an fp16 scale)
+                            (g.c.head_dim * llmi::dtype_size(g.c.kv_dtype) + (g.c.kv_dtype == LLMI_I8 ? 2 : 0));
     return LLMI_OK;
 }
 
@@ -561,7 +585,8 @@ int llmi_batch_bytes(llmi_batch* b, uint64_t* weight_bytes_per_step, uint64_t* k
     if (weight_bytes_per_step)
         *weight_bytes_per_step = g.stream_bytes + (n_act > 1 ? (n_act - 1) * wo * g.c.layers : 0);
     if (kv_bytes_per_pos)
-        *kv_bytes_per_pos = (uint64_t)g.c.layers * g.kvl * g.c.head_dim * 2 * llmi::dtype_size(g.c.kv_dtype);
+        *kv_bytes_per_pos = (uint64_t)g.c.layers * g.kvl * 2 *  // (int8 rows carry an fp16 scale)
+                            (g.c.head_dim * llmi::dtype_size(g.c.kv_dtype) + (g.c.kv_dtype == LLMI_I8 ? 2 : 0));
     return LLMI_OK;
 }
 

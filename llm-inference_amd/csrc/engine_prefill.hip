@@ -77,6 +77,7 @@ PrefillAttnArgs Engine::prefill_attn_args(int l, int m, int p0) const {
     pa.k_cache = kv_layer(l, 0);
     pa.v_cache = kv_layer(l, 1);
     pa.cache_dtype = c.kv_dtype; pa.max_seq = c.max_seq; pa.m = m; pa.p0 = p0;
+    pa.k_scale = kv_scale_layer(l, 0); pa.v_scale = kv_scale_layer(l, 1);
     pa.heads = hl; pa.kv_heads = kvl; pa.head_dim = c.head_dim; pa.rope_tab = rope_tab; pa.out = pf_o;
     return pa;
 }

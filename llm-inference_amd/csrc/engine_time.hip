@@ -80,8 +80,9 @@ int llmi_engine_time_kernel(llmi_engine* e, int which, int iters, float* avg_us,
     auto attn_bytes = [&](uint64_t* out) -> int {  // the K/V rows read up to the device's position, one row written
         llmi::DecodeState hs;
         LLMI_HIP(hipMemcpy(&hs, g.st, sizeof(hs), hipMemcpyDeviceToHost));
-        const uint64_t eb = llmi::dtype_size(g.c.kv_dtype);
-        *out = (uint64_t)2 * (hs.cur_pos + 1) * g.kvl * g.c.head_dim * eb + 2ull * g.kvl * g.c.head_dim * eb;
+        // a row's bytes: its elements, and with the int8 cache its fp16 scale
+        const uint64_t rb = (uint64_t)g.c.head_dim * llmi::dtype_size(g.c.kv_dtype) + (g.kscale ? 2 : 0);
+        *out = (uint64_t)2 * (hs.cur_pos + 1) * g.kvl * rb + 2ull * g.kvl * rb;
         return LLMI_OK;
     };
     switch (which) {
@@ -114,6 +115,7 @@ int llmi_engine_time_kernel(llmi_engine* e, int which, int iters, float* avg_us,
     // cycle through (from the last layer's q/k/v): keep each layer's row at cur_pos
     llmi::DecodeState hst{};
     std::vector<char> save_kv;
+    std::vector<uint16_t> save_ks;
     const size_t kv_eb = llmi::dtype_size(g.c.kv_dtype), kv_row = (size_t)g.c.head_dim * kv_eb;
     const size_t kv_pitch = (size_t)g.c.max_seq * kv_row;
     auto kv_rows = [&](int l, int v) { return g.kv_layer(l, v) + (size_t)hst.cur_pos * kv_row; };
@@ -123,6 +125,13 @@ int llmi_engine_time_kernel(llmi_engine* e, int which, int iters, float* avg_us,
         LLMI_HIP(hipMemcpyAsync(&hst, g.st, sizeof(hst), hipMemcpyDeviceToHost, g.stream));
         LLMI_HIP(hipStreamSynchronize(g.stream));
         save_kv.resize((size_t)g.c.layers * 2 * g.kvl * kv_row);
+        if (g.kscale) {  // int8 cache: the rows' scales too
+            save_ks.resize((size_t)g.c.layers * 2 * g.kvl);
+            for (int l = 0; l < g.c.layers; ++l)
+                for (int v = 0; v < 2; ++v)
+                    LLMI_HIP(hipMemcpy2D(save_ks.data() + ((size_t)l * 2 + v) * g.kvl, 2, g.kv_scale_layer(l, v) + hst.cur_pos,
+                                         (size_t)g.c.max_seq * 2, 2, g.kvl, hipMemcpyDeviceToHost));
+        }
         for (int l = 0; l < g.c.layers; ++l)
             for (int v = 0; v < 2; ++v)
                 LLMI_HIP(hipMemcpy2D(save_kv.data() + ((size_t)l * 2 + v) * g.kvl * kv_row, kv_row, kv_rows(l, v),
@@ -163,6 +172,11 @@ int llmi_engine_time_kernel(llmi_engine* e, int which, int iters, float* avg_us,
             for (int v = 0; v < 2; ++v)
                 LLMI_HIP(hipMemcpy2D(kv_rows(l, v), kv_pitch, save_kv.data() + ((size_t)l * 2 + v) * g.kvl * kv_row,
                                      kv_row, kv_row, g.kvl, hipMemcpyHostToDevice));
+    if ((which == 1 || which == 11) && g.kscale)
+        for (int l = 0; l < g.c.layers; ++l)
+            for (int v = 0; v < 2; ++v)
+                LLMI_HIP(hipMemcpy2D(g.kv_scale_layer(l, v) + hst.cur_pos, (size_t)g.c.max_seq * 2,
+                                     save_ks.data() + ((size_t)l * 2 + v) * g.kvl, 2, 2, g.kvl, hipMemcpyHostToDevice));
     if (which == 10) {  // accumulators back, every layer's counters zero again
         LLMI_HIP(hipMemcpy(g.rl_acc, save_rl.data(), save_rl.size(), hipMemcpyHostToDevice));
         LLMI_HIP(hipMemset(g.rl_cnt, 0, (size_t)g.c.layers * llmi::kRingCntWords * 4));

@@ -49,7 +49,8 @@ int Engine::init(const llmi_config& cfg, int dev, const void* tp_id, hipStream_t
     LLMI_REQUIRE(c.heads % W == 0 && c.kv_heads % W == 0 && c.inter % W == 0 && c.vocab % W == 0,
                  "engine: heads, kv_heads, inter and vocab must divide by tp_world");
     LLMI_REQUIRE(c.max_seq > 0 && c.layers > 0 && c.vocab > 0, "engine: bad dims");
-    LLMI_REQUIRE(c.kv_dtype == LLMI_F16 || c.kv_dtype == LLMI_F32, "engine: kv dtype must be f16/f32");
+    LLMI_REQUIRE(c.kv_dtype == LLMI_F16 || c.kv_dtype == LLMI_F32 || c.kv_dtype == LLMI_I8,
+                 "engine: kv dtype must be f16, f32 or i8");
     wdt = c.weight_dtype;
     LLMI_REQUIRE(wdt == LLMI_F16 || wdt == LLMI_F32 || wdt == LLMI_I8 || wdt == LLMI_I4, "engine: bad weight dtype");
     if (wdt == LLMI_I4 && (W != 1 || ext_stream != nullptr)) {
@@ -162,11 +163,15 @@ int Engine::alloc_weights() {
 int Engine::alloc_state() {
     const size_t H = c.hidden;
     kv_layer_elems = (size_t)kvl * c.max_seq * c.head_dim;
-    const size_t kvb = (size_t)c.layers * kv_layer_elems * dtype_size(c.kv_dtype);
+    const size_t kvb = kv_alloc_bytes();  // int8: the rows, then their fp16 scales (zero: a zero row)
     LLMI_HIP(hipMalloc(&kcache, kvb));
     LLMI_HIP(hipMalloc(&vcache, kvb));
     LLMI_HIP(hipMemsetAsync(kcache, 0, kvb, stream));
     LLMI_HIP(hipMemsetAsync(vcache, 0, kvb, stream));
+    if (kv_scale_bytes()) {
+        kscale = reinterpret_cast<__half*>((char*)kcache + kv_align(kv_data_bytes()));
+        vscale = reinterpret_cast<__half*>((char*)vcache + kv_align(kv_data_bytes()));
+    }
 
     GemvArgs lmargs = lm_args();
     lm_grid = gemv_grid(lmargs);

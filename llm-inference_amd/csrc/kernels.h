@@ -269,7 +269,9 @@ struct PrefillAttnArgs {
     const float* qkv2 = nullptr;   // optional second K slice of qkv (same layout), added first
     void* k_cache = nullptr;       // layer base [kv_heads, max_seq, D]
     void* v_cache = nullptr;
-    int cache_dtype = LLMI_F16;
+    int cache_dtype = LLMI_F16;    // LLMI_I8 (KV8): the scalar form only, with the scales below
+    __half* k_scale = nullptr;     // int8 cache: layer base [kv_heads, max_seq] fp16 row scales
+    __half* v_scale = nullptr;
     int max_seq = 0;
     int m = 0, p0 = 0;
     int heads = 0, kv_heads = 0, head_dim = 128;
@@ -308,7 +310,10 @@ struct AttnArgs {
     const float* qkv = nullptr;    // [(heads + 2 kv_heads) * D]
     void* k_cache = nullptr;       // layer base: [kv_heads, max_seq, D]
     void* v_cache = nullptr;
-    int cache_dtype = LLMI_F16;
+    int cache_dtype = LLMI_F16;    // LLMI_F16, LLMI_F32, or LLMI_I8 (KV8: int8 rows + the scales below)
+    // int8 cache: one fp16 scale per cached row, layer base [kv_heads, max_seq] (include/llmi.h, KV8)
+    __half* k_scale = nullptr;
+    __half* v_scale = nullptr;
     int max_seq = 0;
     const int* pos_dev = nullptr;  // device position (engine); else pos_host
     int pos_host = 0;

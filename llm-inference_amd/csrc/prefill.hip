@@ -36,14 +36,49 @@ __device__ __forceinline__ void store_c(__half* p, float v) { *p = __float2half(
 __device__ __forceinline__ void store_c(float* p, float v) { *p = v; }
 __device__ __forceinline__ float load_c(const __half* p) { return __half2float(*p); }
 __device__ __forceinline__ float load_c(const float* p) { return *p; }
+__device__ __forceinline__ float load_c(const int8_t* p) { return (float)*p; }  // the integer; x the row's scale
+
+// ---- int8 cache (KV8, include/llmi.h): a row of 128 int8 and one fp16 scale, quant.hip's W8A16
+// rule on the row (the decode kernel's q8_scale_bits / q8_quant, attn_impl.h, restated here)
+template <typename KT> constexpr bool kQ8 = sizeof(KT) == 1;
+__device__ __forceinline__ uint32_t q8_abs_bits(float v) { return __float_as_uint(v) & 0x7FFFFFFFu; }
+__device__ __forceinline__ unsigned short q8_scale_bits(uint32_t amax_bits) {
+    if (amax_bits >= 0x7F800000u) return 0x7E00;  // a NaN / infinity in the row: NaN scale, q = 0
+    unsigned short sb = __half_as_ushort(__float2half_rn(__fdiv_rn(__uint_as_float(amax_bits), 127.0f)));
+    if (sb == 0) sb = 1;
+    else if (sb == 0x7C00) sb = 0x7BFF;
+    return sb;
+}
+__device__ __forceinline__ uint32_t q8_pack4(const float* x, unsigned short sb) {
+    if (sb == 0x7E00) return 0u;
+    const float s = __half2float(__ushort_as_half(sb));
+    uint32_t r = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float q = fminf(fmaxf(rintf(__fdiv_rn(x[j], s)), -127.f), 127.f);
+        r |= ((uint32_t)(int)q & 0xFFu) << (8 * j);
+    }
+    return r;
+}
+// maximum over the aligned group of W lanes (16: a k row's work items, 32: a v row's)
+template <int W>
+__device__ __forceinline__ uint32_t group_max_u32(uint32_t v) {
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, o, 64));
+    return v;
+}
 
 // grid (M), block 256: row m of qkv [M, (heads + 2 kv) * D]; with qkv2 (the second
 // K slice of the qkv GEMM) each element is qkv + qkv2 first, and the summed, rotated q
 // is what stays in qkv. Thread work item e: head e / 16, dims 4 (e % 16) .. + 3 and
 // their RoPE partners + 64, as float4s (the pair expression is the decode kernel's).
+// int8 cache: a head's 16 work items are one aligned 16-lane group (the block is a multiple of
+// 64 lanes and the item count a multiple of 16), a v row's 32 items one aligned 32-lane group, so
+// the row maximum is a butterfly inside the group and the row is stored from registers.
 template <typename KT>
 __global__ void rope_kv_prefill_kernel(float* qkv, const float* qkv2, int ld, int p0, int heads, int kv_heads,
-                                       const float* rope_tab, KT* k_cache, KT* v_cache, int max_seq) {
+                                       const float* rope_tab, KT* k_cache, KT* v_cache, int max_seq,
+                                       __half* k_scale, __half* v_scale) {
     const int m = blockIdx.x, pos = p0 + m;
     float* row = qkv + (size_t)m * ld;
     const float* row2 = qkv2 ? qkv2 + (size_t)m * ld : nullptr;
@@ -72,10 +107,20 @@ __global__ void rope_kv_prefill_kernel(float* qkv, const float* qkv2, int ld, in
             *reinterpret_cast<float4*>(p + i + D / 2) = make_float4(r1[0], r1[1], r1[2], r1[3]);
         } else {
             KT* kc = k_cache + ((size_t)(hh - heads) * max_seq + pos) * D;
+            if constexpr (kQ8<KT>) {
+                uint32_t mx = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) mx = max(mx, max(q8_abs_bits(r0[j]), q8_abs_bits(r1[j])));
+                const unsigned short sb = q8_scale_bits(group_max_u32<16>(mx));
+                *reinterpret_cast<uint32_t*>(kc + i) = q8_pack4(r0, sb);
+                *reinterpret_cast<uint32_t*>(kc + i + D / 2) = q8_pack4(r1, sb);
+                if (i == 0) k_scale[(size_t)(hh - heads) * max_seq + pos] = __ushort_as_half(sb);
+            } else {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 store_c(kc + i + j, r0[j]);
                 store_c(kc + i + j + D / 2, r1[j]);
+            }
             }
         }
     }
@@ -88,10 +133,18 @@ __global__ void rope_kv_prefill_kernel(float* qkv, const float* qkv2, int ld, in
             v.x += y.x; v.y += y.y; v.z += y.z; v.w += y.w;
         }
         KT* vc = v_cache + ((size_t)hh * max_seq + pos) * D + d;
+        if constexpr (kQ8<KT>) {
+            const float x[4] = {v.x, v.y, v.z, v.w};
+            const uint32_t mx = max(max(q8_abs_bits(v.x), q8_abs_bits(v.y)), max(q8_abs_bits(v.z), q8_abs_bits(v.w)));
+            const unsigned short sb = q8_scale_bits(group_max_u32<32>(mx));
+            *reinterpret_cast<uint32_t*>(vc) = q8_pack4(x, sb);
+            if (d == 0) v_scale[(size_t)hh * max_seq + pos] = __ushort_as_half(sb);
+        } else {
         store_c(vc, v.x);
         store_c(vc + 1, v.y);
         store_c(vc + 2, v.z);
         store_c(vc + 3, v.w);
+        }
     }
 }
 
@@ -102,7 +155,8 @@ template <typename KT>
 __global__ __launch_bounds__(kThreads) void attn_prefill_kernel(const float* qkv, int ld, int m_rows, int p0,
                                                                 int heads, int kv_heads, const KT* k_cache,
                                                                 const KT* v_cache, int max_seq, float* out,
-                                                                int ldo) {
+                                                                int ldo, const __half* k_scale,
+                                                                const __half* v_scale) {
     __shared__ float q_s[QB * kLdq];
     __shared__ float k_s[KC * kLdq];
     __shared__ float v_s[KC * D];
@@ -126,6 +180,8 @@ __global__ __launch_bounds__(kThreads) void attn_prefill_kernel(const float* qkv
 
     const KT* kc = k_cache + (size_t)kvh * max_seq * D;
     const KT* vc = v_cache + (size_t)kvh * max_seq * D;
+    const __half* ksc = kQ8<KT> ? k_scale + (size_t)kvh * max_seq : nullptr;  // int8 cache: the rows' scales
+    const __half* vsc = kQ8<KT> ? v_scale + (size_t)kvh * max_seq : nullptr;
     const int my_pos = p0 + q_row;
     const int kend = p0 + min(q_first + QB, m_rows);  // keys [0, kend)
 
@@ -139,8 +195,13 @@ __global__ __launch_bounds__(kThreads) void attn_prefill_kernel(const float* qkv
         for (int e = t; e < KC * D; e += kThreads) {
             const int r = e / D, d = e % D;
             const int j = min(k0 + r, kend - 1);
+            if constexpr (kQ8<KT>) {  // q * s: exact in fp32
+                k_s[r * kLdq + d] = load_c(kc + (size_t)j * D + d) * __half2float(ksc[j]);
+                v_s[r * D + d] = load_c(vc + (size_t)j * D + d) * __half2float(vsc[j]);
+            } else {
             k_s[r * kLdq + d] = load_c(kc + (size_t)j * D + d);
             v_s[r * D + d] = load_c(vc + (size_t)j * D + d);
+            }
         }
         __syncthreads();
 
@@ -702,8 +763,11 @@ int prefill_attn_check(const PrefillAttnArgs& a) {
                                         (a.out || a.out_hi)),
                  "prefill attention: the MFMA form needs the fp16 cache, 1 or 2 planes and an output");
     LLMI_REQUIRE(a.mfma_planes != 0 || a.out, "prefill attention: null output");
-    LLMI_REQUIRE(a.cache_dtype == LLMI_F16 || a.cache_dtype == LLMI_F32,
-                 "prefill attention: cache dtype must be f16 or f32");
+    LLMI_REQUIRE(a.cache_dtype == LLMI_F16 || a.cache_dtype == LLMI_F32 || a.cache_dtype == LLMI_I8,
+                 "prefill attention: cache dtype must be f16, f32 or i8");
+    LLMI_REQUIRE(a.cache_dtype != LLMI_I8 || (a.k_scale && a.v_scale && (uintptr_t)a.k_cache % 4 == 0 &&
+                                              (uintptr_t)a.v_cache % 4 == 0),
+                 "prefill attention: an int8 cache needs its row scales (k_scale, v_scale) and 4-byte alignment");
     return LLMI_OK;
 }
 }  // namespace
@@ -768,7 +832,8 @@ int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
     const dim3 ga((a.m + QB - 1) / QB, a.heads);
     if (a.cache_dtype == LLMI_F16) {
         hipLaunchKernelGGL(rope_kv_prefill_kernel<__half>, dim3(a.m), dim3(pf_rope_threads()), 0, s, a.qkv, a.qkv2, ld, a.p0, a.heads,
-                           a.kv_heads, a.rope_tab, (__half*)a.k_cache, (__half*)a.v_cache, a.max_seq);
+                           a.kv_heads, a.rope_tab, (__half*)a.k_cache, (__half*)a.v_cache, a.max_seq, (__half*)nullptr,
+                           (__half*)nullptr);
         if (a.mfma_planes) {
             const int nqb = (a.m + QM - 1) / QM;
             const int cb = plan.cb, maxc = plan.maxc;
@@ -798,14 +863,22 @@ int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
         } else {
             hipLaunchKernelGGL(attn_prefill_kernel<__half>, ga, dim3(kThreads), 0, s, a.qkv, ld, a.m, a.p0, a.heads,
                                a.kv_heads, (const __half*)a.k_cache, (const __half*)a.v_cache, a.max_seq, a.out,
-                               a.heads * D);
+                               a.heads * D, (const __half*)nullptr, (const __half*)nullptr);
         }
+    } else if (a.cache_dtype == LLMI_I8) {
+        hipLaunchKernelGGL(rope_kv_prefill_kernel<int8_t>, dim3(a.m), dim3(pf_rope_threads()), 0, s, a.qkv, a.qkv2, ld,
+                           a.p0, a.heads, a.kv_heads, a.rope_tab, (int8_t*)a.k_cache, (int8_t*)a.v_cache, a.max_seq,
+                           a.k_scale, a.v_scale);
+        hipLaunchKernelGGL(attn_prefill_kernel<int8_t>, ga, dim3(kThreads), 0, s, a.qkv, ld, a.m, a.p0, a.heads,
+                           a.kv_heads, (const int8_t*)a.k_cache, (const int8_t*)a.v_cache, a.max_seq, a.out,
+                           a.heads * D, (const __half*)a.k_scale, (const __half*)a.v_scale);
     } else {
         hipLaunchKernelGGL(rope_kv_prefill_kernel<float>, dim3(a.m), dim3(pf_rope_threads()), 0, s, a.qkv, a.qkv2, ld, a.p0, a.heads,
-                           a.kv_heads, a.rope_tab, (float*)a.k_cache, (float*)a.v_cache, a.max_seq);
+                           a.kv_heads, a.rope_tab, (float*)a.k_cache, (float*)a.v_cache, a.max_seq, (__half*)nullptr,
+                           (__half*)nullptr);
         hipLaunchKernelGGL(attn_prefill_kernel<float>, ga, dim3(kThreads), 0, s, a.qkv, ld, a.m, a.p0, a.heads,
                            a.kv_heads, (const float*)a.k_cache, (const float*)a.v_cache, a.max_seq, a.out,
-                           a.heads * D);
+                           a.heads * D, (const __half*)nullptr, (const __half*)nullptr);
     }
     LLMI_HIP(hipGetLastError());
     return LLMI_OK;

@@ -63,7 +63,7 @@ class DebugAttnOprojArgs(C.Structure):
                 ("xacc", C.c_void_p), ("resid", C.c_void_p), ("resid_fixed", C.c_void_p),
                 ("resid_scale", C.c_float), ("w", C.c_void_p), ("scales", C.c_void_p),
                 ("w_dtype", C.c_int), ("head_major", C.c_int), ("n_rows", C.c_int), ("ldw", C.c_int),
-                ("err", C.c_void_p)]
+                ("err", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
 
 
 class DebugPrefillAttnArgs(C.Structure):
@@ -73,7 +73,8 @@ class DebugPrefillAttnArgs(C.Structure):
                 ("heads", C.c_int), ("kv_heads", C.c_int), ("head_dim", C.c_int),
                 ("rope_tab", C.c_void_p), ("out", C.c_void_p), ("mfma_planes", C.c_int),
                 ("out_hi", C.c_void_p), ("out_lo", C.c_void_p), ("out_lo8", C.c_int),
-                ("split_ws", C.c_void_p), ("split_ws_floats", C.c_size_t), ("chunk_blocks", C.c_int)]
+                ("split_ws", C.c_void_p), ("split_ws_floats", C.c_size_t), ("chunk_blocks", C.c_int),
+                ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
 
 
 _P, _I, _U64, _U32, _F, _SZ = C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_size_t
@@ -92,6 +93,7 @@ _SIGS = {
     "llmi_rope_decode": (_I, [_P, _I, _I, _I, _I, _F, _P]),
     "llmi_attn_workspace_bytes": (_SZ, [_I, _I, _I]),
     "llmi_attn_decode": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "llmi_attn_decode_q8": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
     "llmi_argmax": (_I, [_P, _I, _P, _P]),
     "llmi_topk": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "llmi_sampling": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
@@ -163,6 +165,7 @@ _SIGS = {
     "llmi_engine_logits": (_I, [_P, _P, _I]),
     "llmi_engine_hidden": (_I, [_P, _P, _I]),
     "llmi_engine_kv_slot": (_I, [_P, _I, _I, _I, _P]),
+    "llmi_engine_kv_slot_q8": (_I, [_P, _I, _I, _I, _P, _P]),
     "llmi_engine_bytes": (_I, [_P, C.POINTER(_U64), C.POINTER(_U64)]),
     "llmi_engine_stream": (_P, [_P]),
     "llmi_engine_time_kernel": (_I, [_P, _I, _I, C.POINTER(_F), C.POINTER(_U64)]),

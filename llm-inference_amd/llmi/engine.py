@@ -191,6 +191,14 @@ class Engine:
         call("llmi_engine_kv_slot", self._h, layer, pos, 1 if which_v else 0, out.ctypes.data)
         return out
 
+    def kv_slot_q8(self, layer: int, pos: int, which_v: bool = False):
+        """An int8 cache's slot as stored: (q [kv_heads, head_dim] int8, scale bits [kv_heads] uint16)."""
+        kvl = self.cfg.kv_heads // self.cfg.tp_world
+        q = np.zeros((kvl, self.cfg.head_dim), np.int8)
+        s = np.zeros(kvl, np.uint16)
+        call("llmi_engine_kv_slot_q8", self._h, layer, pos, 1 if which_v else 0, q.ctypes.data, s.ctypes.data)
+        return q, s
+
     def bytes_per_token(self):
         w, kv = C.c_uint64(), C.c_uint64()
         call("llmi_engine_bytes", self._h, C.byref(w), C.byref(kv))

@@ -121,6 +121,26 @@ def launchDecoderMaskedMHA(qkv, k_cache, v_cache, layer: int, pos: int, heads: i
     return out
 
 
+def attn_decode_q8(qkv, k_cache, v_cache, k_scale, v_scale, layer: int, pos: int, heads: int, kv_heads: int,
+                   workspace, rope: bool = False, base: float = 10000.0, head_dim: int = 128):
+    """launchDecoderMaskedMHA over an int8 cache (KV8, include/llmi.h): k_cache / v_cache
+    [layers, kv_heads, max_seq, d] int8, k_scale / v_scale [layers, kv_heads, max_seq] fp16; slot
+    `pos` of `layer` is quantised and written with its scale. Returns out [heads * d] fp32."""
+    _dev(qkv, k_cache, v_cache, k_scale, v_scale, workspace)
+    if k_cache.dtype != torch.int8 or v_cache.dtype != torch.int8:
+        raise TypeError("attn_decode_q8: the caches must be int8")
+    if k_scale.dtype != torch.float16 or v_scale.dtype != torch.float16:
+        raise TypeError("attn_decode_q8: the scales must be float16")
+    max_seq = k_cache.shape[2]
+    if tuple(k_scale.shape) != tuple(k_cache.shape[:3]) or tuple(v_scale.shape) != tuple(v_cache.shape[:3]):
+        raise ValueError("attn_decode_q8: scales must be [layers, kv_heads, max_seq]")
+    out = torch.empty(heads * head_dim, device=qkv.device, dtype=torch.float32)
+    call("llmi_attn_decode_q8", qkv.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), _lib.I8, layer,
+         max_seq, int(pos), heads, kv_heads, head_dim, 1 if rope else 0, float(base), out.data_ptr(),
+         workspace.data_ptr(), _stream(), k_scale.data_ptr(), v_scale.data_ptr())
+    return out
+
+
 def argmax(logits: torch.Tensor) -> torch.Tensor:
     _dev(logits)
     out = torch.empty(1, device=logits.device, dtype=torch.int32)
