@@ -257,6 +257,21 @@ typedef struct llmi_debug_attn_oproj_args {
     void* v_scale; /* NULL: unused (an f16 / f32 cache) */
 } llmi_debug_attn_oproj_args;
 int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t stream);
+/* llmi_debug_attn_oproj_rows: the multi-row attention + o_proj of a speculative verify step --
+ * args[0 .. m), 2 <= m <= 8, are m query rows of ONE sequence at consecutive positions
+ * *args[0].pos_dev + i (the other blocks' pos_dev is not read) against ONE cache and ONE W_o:
+ * one attention launch that loads every cached K / V row once and one o_proj launch that loads
+ * W_o once. Row i sees keys 0 .. p + i; positions p .. p + m - 1 are written to the cache by
+ * this call and never read from it. The blocks must agree in k_cache, v_cache, cache_dtype,
+ * max_seq, heads, kv_heads, head_dim, rope, rope_base, w, scales, w_dtype, head_major, n_rows,
+ * ldw, nact and err (else LLMI_EINVAL) and differ in qkv, workspace, xacc, resid, resid_fixed
+ * and resid_scale; a row with neither resid nor resid_fixed is pre-seeded (its xacc is added
+ * onto as it stands, the engine's form when the down GEMV wrote the seed). nact > 0 must be (*pos_dev + m - 1) / 64 + 1 (a mismatch sets bit 4 in *err
+ * and computes nothing); nact 0 sizes the grid for max_seq. Row i's xacc, partials and cache
+ * row are bitwise those of llmi_debug_attn_oproj(&args[i]) at position p + i, the rows run in
+ * order. m outside 2..8: LLMI_EINVAL; an int8 cache: LLMI_EUNSUPPORTED. Nothing is launched on
+ * an error. */
+int llmi_debug_attn_oproj_rows(const llmi_debug_attn_oproj_args* args, int m, llmi_stream_t stream);
 
 /* Diagnostics (no reference counterpart): while `stamps` (device memory, 8 u64 per
  * workgroup) is non-null, every launch of the transposed prefill attention kernel writes its
@@ -742,6 +757,52 @@ int llmi_engine_logprobs(llmi_engine* e, float* tok_lp, int32_t* top_ids, float*
 int llmi_engine_set_prompt(llmi_engine* e, const int32_t* ids, int n);
 /* Run n forward steps (one token each). use_graph: replay the captured hipGraph. */
 int llmi_engine_decode(llmi_engine* e, int n_steps, int use_graph);
+/* Speculative decoding (no reference counterpart): verify up to 8 positions of ONE sequence in
+ * one pass over the weights and the KV cache, exact -- whatever is kept is bitwise what greedy
+ * llmi_engine_decode produces.
+ *
+ * llmi_engine_set_speculation: max_draft in [0, 7] (else LLMI_EINVAL); allocates max_draft
+ * extra lanes on first use (each its own activations, residual accumulators, attention
+ * workspace, logits and argmax partials; the KV cache, the RoPE table and the weights are the
+ * engine's), none at 0. LLMI_EUNSUPPORTED with max_draft > 0 for tp_world > 1 and group ranks,
+ * int4 weights (the multi-row GEMV has no int4 form), an int8 KV cache, the ring decode mode,
+ * an active sampler (llmi_engine_set_sampling k > 0, llmi_engine_set_sampling_params) and
+ * logprobs; and while max_draft > 0 those setters return LLMI_EUNSUPPORTED in turn. */
+int llmi_engine_set_speculation(llmi_engine* e, int max_draft);
+/* One verify step at p = the next position: the pending token (the argmax the last forward
+ * left, as a decode step would pick it) at p and draft[i - 1] at p + i run through the model as
+ * n_draft + 1 rows -- per layer one multi-row GEMV each for q/k/v, gate_up and down, ONE
+ * multi-row attention launch and ONE multi-row o_proj launch, then one multi-row lm_head.
+ * With g_i the argmax of row i (ties to the lowest id), a = the largest value with
+ * draft[j] == g_j for all j < a is accepted on the device, and the engine is left exactly
+ * where a + 1 llmi_engine_decode steps would have left it: next position p + a + 1, tokens
+ * p .. p + a, and row a's argmax partials, logits and hidden state. Cache rows p + a + 1 ..
+ * p + n_draft hold rejected k / v; nothing reads them before they are overwritten. The call
+ * synchronises and reads a few bytes back; *n_accepted = a. n_draft 0 runs the plain step.
+ * Needs the prompt consumed, 0 <= n_draft <= max_draft, draft ids inside the vocabulary and
+ * p + n_draft + 1 <= max_seq (else LLMI_EINVAL, nothing changed). use_graph: replay graphs
+ * captured per (n_draft + 1, split count of p + n_draft). */
+int llmi_engine_verify(llmi_engine* e, const int32_t* draft, int n_draft, int use_graph, int* n_accepted);
+/* Prompt-lookup drafting, on the host (no GPU, no engine): for g = ngram_max down to ngram_min
+ * with g <= n - 1, the suffix ids[n - g .. n) is searched among the starts 0 <= s <= n - g - 1;
+ * the first g with a match wins and the LARGEST matching s is taken; the draft is
+ * ids[s + g .. min(n, s + g + max_draft)) (it may run into the suffix itself). No match:
+ * *n_out = 0. out holds max_draft ids. LLMI_EINVAL: a null pointer, ngram_min < 1,
+ * ngram_max < ngram_min, max_draft outside [0, 7], n < 0. */
+int llmi_lookup_draft(const int32_t* ids, int n, int ngram_max, int ngram_min, int max_draft, int32_t* out,
+                      int* n_out);
+/* Greedy generation with prompt-lookup drafts: advances the engine by exactly n_steps positions
+ * and ends in bitwise the state llmi_engine_decode(e, n_steps, .) ends in. Each round drafts
+ * (llmi_lookup_draft) from the sequence so far plus the pending token, trims the draft to
+ * min(max_draft, remaining - 1, max_seq - p - 1) and calls llmi_engine_verify. The host keeps
+ * its own copy of the token history (one read of the tokens at the start, then the accepted
+ * counts). Needs the prompt consumed and llmi_engine_set_speculation(>= max_draft). stats
+ * (nullable): verify steps run, ids drafted, ids accepted; verify_steps + accepted = n_steps. */
+typedef struct llmi_spec_stats {
+    int verify_steps, drafted, accepted;
+} llmi_spec_stats;
+int llmi_engine_generate_lookup(llmi_engine* e, int n_steps, int max_draft, int ngram_max, int ngram_min,
+                                int use_graph, llmi_spec_stats* stats);
 /* Prefill (Llama<T>::firstTokenGen, llama.cpp:273-316; LlamaContextDecoder::forward,
  * context_decoder.cpp:47-143): the next n_tokens prompt rows in one batched pass
  * (chunks of 512) -- MFMA GEMMs, causal prefill attention, KV slots written --

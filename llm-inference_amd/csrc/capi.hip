@@ -203,6 +203,55 @@ int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t 
     return attn_oproj_launch(o, STREAM(stream));
 }
 
+int llmi_debug_attn_oproj_rows(const llmi_debug_attn_oproj_args* args, int m, llmi_stream_t stream) {
+    LLMI_REQUIRE(args != nullptr, "debug_attn_oproj_rows: null arguments");
+    LLMI_REQUIRE(m >= 2 && m <= kAttnRowsMax, "debug_attn_oproj_rows: m must be 2..8");
+    const llmi_debug_attn_oproj_args& z = args[0];
+    LLMI_REQUIRE(z.pos_dev && z.err && z.n_rows > 0, "debug_attn_oproj_rows: pos_dev, err and n_rows needed");
+    if (z.cache_dtype == LLMI_I8) {
+        set_last_error("[llmi][ERROR] debug_attn_oproj_rows: an int8 cache is a single-row form");
+        return LLMI_EUNSUPPORTED;
+    }
+    AttnRowsArgs at;
+    OprojRowsArgs o;
+    at.m = o.m = m;
+    for (int i = 0; i < m; ++i) {
+        const llmi_debug_attn_oproj_args& d = args[i];
+        LLMI_REQUIRE(d.k_cache == z.k_cache && d.v_cache == z.v_cache && d.cache_dtype == z.cache_dtype &&
+                         d.max_seq == z.max_seq && d.heads == z.heads && d.kv_heads == z.kv_heads &&
+                         d.head_dim == z.head_dim && d.rope == z.rope && d.rope_base == z.rope_base && d.w == z.w &&
+                         d.scales == z.scales && d.w_dtype == z.w_dtype && d.head_major == z.head_major &&
+                         d.n_rows == z.n_rows && d.ldw == z.ldw && d.nact == z.nact && d.err == z.err,
+                     "debug_attn_oproj_rows: the rows must share the caches, shapes, rope, W_o, nact and err");
+        LLMI_REQUIRE(d.qkv && d.workspace && d.xacc, "debug_attn_oproj_rows: a row's qkv, workspace or xacc is null");
+        AttnRow& r = at.row[i];
+        r.qkv = d.qkv; r.workspace = d.workspace; r.xacc = d.xacc;
+        r.resid = d.resid; r.resid_fixed = d.resid_fixed; r.resid_scale = d.resid_scale;
+        o.row[i] = r;
+        // neither seed source: xacc is pre-seeded (the engine's form when the down GEMV wrote it)
+        if (!d.resid && !d.resid_fixed) r.xacc = nullptr;
+    }
+    AttnArgs& a = at.a;
+    a.k_cache = z.k_cache; a.v_cache = z.v_cache; a.cache_dtype = z.cache_dtype;
+    a.max_seq = z.max_seq; a.pos_dev = z.pos_dev; a.nact = z.nact;
+    a.heads = z.heads; a.kv_heads = z.kv_heads; a.head_dim = z.head_dim ? z.head_dim : 128;
+    a.rope = z.rope; a.rope_base = z.rope_base != 0.f ? z.rope_base : 10000.f;
+    a.direct_out = 0;
+    a.hidden = z.n_rows;
+    a.err = z.err;
+    OprojArgs& w = o.a;
+    w.w = z.w; w.scales = reinterpret_cast<const __half*>(z.scales); w.w_dtype = z.w_dtype;
+    w.head_major = z.head_major; w.n_rows = z.n_rows; w.ldw = z.ldw;
+    w.heads = z.heads; w.head_dim = a.head_dim; w.max_seq = z.max_seq;
+    w.pos_dev = z.pos_dev; w.nact = z.nact; w.err = z.err;
+    // both argument checks before either launch (as llmi_debug_attn_oproj)
+    LLMI_REQUIRE(w.w && w.ldw >= w.heads * 128 && w.ldw % 16 == 0 && (w.w_dtype != LLMI_I8 || w.scales) &&
+                     (w.w_dtype == LLMI_F16 || w.w_dtype == LLMI_F32 || w.w_dtype == LLMI_I8),
+                 "debug_attn_oproj_rows: bad W_o arguments");
+    LLMI_TRY(attn_rows_launch(at, STREAM(stream)));
+    return oproj_rows_launch(o, STREAM(stream));
+}
+
 int llmi_debug_prefill_stamps(void* stamps) {
     prefill_stamps_debug(static_cast<unsigned long long*>(stamps));
     return LLMI_OK;

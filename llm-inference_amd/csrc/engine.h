@@ -311,6 +311,20 @@ struct Engine {
     int32_t* lp_ids() const { return reinterpret_cast<int32_t*>(lp_buf + lp_records() * 4); }
     float* lp_tlp() const { return reinterpret_cast<float*>(lp_buf + lp_records() * 4 * (1 + kLpMaxTop)); }
 
+    // -------------------------------------------------------- speculation
+    // llmi_engine_set_speculation (engine_spec.hip): spec_max extra lanes, each an Engine on this
+    // stream that borrows the weights (init's lender) and -- kv_from -- the KV cache and the RoPE
+    // table, with its own DecodeState, x, q/k/v, activations, residual accumulators, attention
+    // workspace, logits and argmax partials. spec_draft: device [8] draft ids, then {a, g_a, error}.
+    // spec_graphs: captured verify steps by (rows, split count of the last row); bounded, a full
+    // cache is dropped whole (after a sync) before the next capture
+    const Engine* kv_from = nullptr;
+    int spec_max = 0;
+    std::vector<std::unique_ptr<Engine>> lanes;
+    int32_t* spec_draft = nullptr;
+    static constexpr size_t kMaxSpecGraphs = 64;
+    std::map<std::pair<int, int>, std::pair<hipGraph_t, hipGraphExec_t>> spec_graphs;
+
     // -------------------------------------------------------------- debug
     unsigned long long* dbg_stamps = nullptr;  // llmi_engine_debug_stamps: per-workgroup timeline
     // llmi_engine_debug_timeline: every stamped launch of a recorded step gets its own
@@ -403,7 +417,20 @@ struct Engine {
     int score_chunk(int m, int p0, int split, bool use_gemm2, bool last);
     int prefill(int n, int split, bool scored = false);
     int scored_logits_out(int pos, float* out, int n);
+
+    // ---- engine_spec.hip: speculative decoding (the verify step, the lookup generation loop)
+    void clear_spec_graphs();
+    const char* spec_refusal() const;
+    int set_speculation(int max_draft);
+    template <typename F>
+    int spec_rows(int m, F&& args_of);  // engine_spec.hip, its only user
+    int record_verify(int m);
+    int verify(const int32_t* draft, int n_draft, int use_graph, int* n_accepted, int* next_token = nullptr);
+    int generate_lookup(int n_steps, int max_draft, int ngram_max, int ngram_min, int use_graph,
+                        llmi_spec_stats* stats);
 };
+// prompt-lookup drafting on the host (llmi_lookup_draft)
+int lookup_draft(const int32_t* ids, int n, int ngram_max, int ngram_min, int max_draft, int32_t* out, int* n_out);
 
 // In-process tensor-parallel group: W rank engines (tp_rank 0..W-1) on ONE
 // device and ONE stream, stepped phase by phase with group_reduce_kernel in

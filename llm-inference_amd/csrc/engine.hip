@@ -315,6 +315,10 @@ int Engine::set_option(const std::string& name, int value) {
 int Engine::set_sampling(int k, uint64_t sd) {
     LLMI_REQUIRE(k >= 0 && k <= 16, "set_sampling: k must be in [0, 16] (0 = greedy)");
     LLMI_REQUIRE(k == 0 || (c.tp_world == 1 && !grouped), "set_sampling: sampling needs the full logits (tp_world 1)");
+    if (k > 0 && spec_max > 0) {
+        set_last_error("[llmi][ERROR] set_sampling: speculation is on (greedy only; set_speculation 0 first)");
+        return LLMI_EUNSUPPORTED;
+    }
     if (k > 0 && !samp_ids) {
         LLMI_HIP(hipMalloc(&samp_ids, 16 * sizeof(int32_t)));
         LLMI_HIP(hipMalloc(&samp_vals, 16 * sizeof(float)));
@@ -331,6 +335,10 @@ int Engine::set_sampling(int k, uint64_t sd) {
 int Engine::set_sampling_params(const llmi_sampling_params& p) {
     LLMI_REQUIRE(c.tp_world == 1 && !grouped, "set_sampling_params: sampling needs the full logits (tp_world 1)");
     LLMI_TRY(engine_nucleus_check(c.vocab, p.repetition_penalty, p.temperature, p.top_k, p.top_p));
+    if (spec_max > 0) {
+        set_last_error("[llmi][ERROR] set_sampling_params: speculation is on (greedy only; set_speculation 0 first)");
+        return LLMI_EUNSUPPORTED;
+    }
     LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
     graphs.clear();                          // the captured step changes
     nuc = p;
@@ -349,6 +357,11 @@ int Engine::set_logprobs(int n_top) {
             return LLMI_EUNSUPPORTED;
         }
         LLMI_TRY(engine_logprob_check(c.vocab, n_top));
+        if (spec_max > 0) {
+            set_last_error("[llmi][ERROR] set_logprobs: speculation is on (the verify step records none; "
+                           "set_speculation 0 first)");
+            return LLMI_EUNSUPPORTED;
+        }
     }
     LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
     graphs.clear();                          // the captured step changes
@@ -388,6 +401,10 @@ int Engine::set_decode_mode(int mode) {
     LLMI_HIP(hipStreamSynchronize(stream));
     if (mode == 1 && wdt == LLMI_I4) {
         set_last_error("[llmi][ERROR] set_decode_mode: the ring layer streams fp16 weights; int4 engines run mode 0");
+        return LLMI_EUNSUPPORTED;
+    }
+    if (mode == 1 && spec_max > 0) {
+        set_last_error("[llmi][ERROR] set_decode_mode: speculation is on (the ring layer has no verify step)");
         return LLMI_EUNSUPPORTED;
     }
     if (mode == 1) {

@@ -166,6 +166,30 @@ int llmi_engine_decode(llmi_engine* e, int n_steps, int use_graph) {
     return e->e.decode(n_steps, use_graph);
 }
 
+int llmi_engine_set_speculation(llmi_engine* e, int max_draft) {
+    LLMI_REQUIRE(e, "engine_set_speculation: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.set_speculation(max_draft);
+}
+
+int llmi_engine_verify(llmi_engine* e, const int32_t* draft, int n_draft, int use_graph, int* n_accepted) {
+    LLMI_REQUIRE(e, "engine_verify: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.verify(draft, n_draft, use_graph, n_accepted);
+}
+
+int llmi_lookup_draft(const int32_t* ids, int n, int ngram_max, int ngram_min, int max_draft, int32_t* out,
+                      int* n_out) {
+    return llmi::lookup_draft(ids, n, ngram_max, ngram_min, max_draft, out, n_out);
+}
+
+int llmi_engine_generate_lookup(llmi_engine* e, int n_steps, int max_draft, int ngram_max, int ngram_min,
+                                int use_graph, llmi_spec_stats* stats) {
+    LLMI_REQUIRE(e, "engine_generate_lookup: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.generate_lookup(n_steps, max_draft, ngram_max, ngram_min, use_graph, stats);
+}
+
 int llmi_engine_prefill(llmi_engine* e, int n_tokens, int exact) {
     LLMI_REQUIRE(e, "null engine");
     LLMI_REQUIRE(exact >= 0 && exact <= 2, "prefill: exact must be 0 (fp16 A), 1 (fp32-faithful) or 2 (fp8 lo planes)");

@@ -10,6 +10,9 @@ Engine::~Engine() {  // teardown errors are not actionable; ignore them explicit
     if (samp_ids) (void)hipFree(samp_ids);
     if (samp_vals) (void)hipFree(samp_vals);
     graphs.clear();
+    clear_spec_graphs();
+    lanes.clear();  // the verify lanes before what they borrow
+    if (spec_draft) (void)hipFree(spec_draft);
     if (comm) (void)ncclCommDestroy(comm);
     for (void* p : peers_opened) (void)hipIpcCloseMemHandle(p);
     if (inbox) (void)hipFree(inbox);
@@ -17,8 +20,8 @@ Engine::~Engine() {  // teardown errors are not actionable; ignore them explicit
     if (xchg_ep) (void)hipFree(xchg_ep);
     if (xt_cnt) (void)hipFree(xt_cnt);
     if (wblob) (void)hipFree(wblob);
-    if (kcache) (void)hipFree(kcache);
-    if (vcache) (void)hipFree(vcache);
+    if (kcache && !kv_from) (void)hipFree(kcache);  // (a verify lane's cache is its engine's)
+    if (vcache && !kv_from) (void)hipFree(vcache);
     if (scratch) (void)hipFree(scratch);
     if (!pf_from) {  // (a batch slot's are slot 0's)
         if (pf) (void)hipFree(pf);
@@ -164,10 +167,15 @@ int Engine::alloc_state() {
     const size_t H = c.hidden;
     kv_layer_elems = (size_t)kvl * c.max_seq * c.head_dim;
     const size_t kvb = kv_alloc_bytes();  // int8: the rows, then their fp16 scales (zero: a zero row)
-    LLMI_HIP(hipMalloc(&kcache, kvb));
-    LLMI_HIP(hipMalloc(&vcache, kvb));
-    LLMI_HIP(hipMemsetAsync(kcache, 0, kvb, stream));
-    LLMI_HIP(hipMemsetAsync(vcache, 0, kvb, stream));
+    if (kv_from) {  // a verify lane (engine_spec.hip): the engine's cache, nothing allocated
+        kcache = kv_from->kcache;
+        vcache = kv_from->vcache;
+    } else {
+        LLMI_HIP(hipMalloc(&kcache, kvb));
+        LLMI_HIP(hipMalloc(&vcache, kvb));
+        LLMI_HIP(hipMemsetAsync(kcache, 0, kvb, stream));
+        LLMI_HIP(hipMemsetAsync(vcache, 0, kvb, stream));
+    }
     if (kv_scale_bytes()) {
         kscale = reinterpret_cast<__half*>((char*)kcache + kv_align(kv_data_bytes()));
         vscale = reinterpret_cast<__half*>((char*)vcache + kv_align(kv_data_bytes()));
@@ -205,6 +213,11 @@ int Engine::alloc_state() {
     // cos/sin cache with HF's fp32 arithmetic (LlamaRotaryEmbedding._set_cos_sin_cache):
     // inv_freq = 1 / fp32(base ** (2i/d)) (torch's fp32 pow is correctly rounded),
     // angle = fp32(pos * inv_freq), cos/sin correctly rounded to fp32
+    if (kv_from) {  // a verify lane reads the engine's table
+        rope_tab = kv_from->rope_tab;
+        LLMI_HIP(hipStreamSynchronize(stream));
+        return LLMI_OK;
+    }
     std::vector<float> tab((size_t)c.max_seq * c.head_dim);
     const int half = c.head_dim / 2;
     for (int i = 0; i < half; ++i) {

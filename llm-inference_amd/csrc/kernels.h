@@ -378,6 +378,36 @@ struct OprojArgs {
 };
 int attn_oproj_launch(const OprojArgs& a, hipStream_t s);
 
+// ------------------------------- multi-row decode attention + o_proj (attn_rows.hip)
+// m query rows (2..kAttnRowsMax) of ONE sequence at consecutive positions p, p + 1, ...,
+// p + m - 1 (p = the device position) against ONE shared K/V cache: a (head, split)
+// workgroup loads its 64 cached K and V rows once and serves every row; row i sees keys
+// 0 .. p + i, the rows p .. p + i from LDS (never from the cache: this launch writes them).
+// Row i's partials, cache row and xacc are bitwise those of attn_decode_launch /
+// attn_oproj_launch for row i alone at position p + i, run in order. f16 / f32 caches.
+constexpr int kAttnRowsMax = 8;
+struct AttnRow {  // what differs between the rows (AttnArgs' / OprojArgs' fields of the same names)
+    const float* qkv = nullptr;
+    void* workspace = nullptr;
+    long long* xacc = nullptr;
+    const float* resid = nullptr;
+    const long long* resid_fixed = nullptr;
+    float resid_scale = 1.f;
+};
+struct AttnRowsArgs {
+    AttnArgs a;  // the cache side, shapes, rope, pos_dev (row 0's position), nact (of p + m - 1), err
+    int m = 0;
+    AttnRow row[kAttnRowsMax];
+};
+struct OprojRowsArgs {
+    OprojArgs a;  // W_o, its scales and layout, shapes, pos_dev (row 0's position), nact (of p + m - 1)
+    int m = 0;
+    AttnRow row[kAttnRowsMax];  // workspace and xacc used
+};
+// LLMI_EUNSUPPORTED: an int8 cache, the merged output form (direct_out), granule rows, stamps
+int attn_rows_launch(const AttnRowsArgs& p, hipStream_t s);
+int oproj_rows_launch(const OprojRowsArgs& p, hipStream_t s);
+
 // Persistent ring layer (ring.hip): after layer l's attention, ONE launch runs
 //   o_proj (merge fused, by head) -> RMSNorm + gate_up + SiLU*up -> down (K split by CU)
 //   -> [RMSNorm + next layer's q/k/v]

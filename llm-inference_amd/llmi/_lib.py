@@ -39,6 +39,11 @@ class SamplingParams(C.Structure):
                 ("repetition_penalty", C.c_float), ("seed", C.c_uint64)]
 
 
+class SpecStats(C.Structure):
+    """llmi_spec_stats (include/llmi.h), field for field."""
+    _fields_ = [("verify_steps", C.c_int), ("drafted", C.c_int), ("accepted", C.c_int)]
+
+
 class DebugGemvArgs(C.Structure):
     """llmi_debug_gemv_args (include/llmi.h), field for field; pointers are device addresses."""
     _fields_ = [("w", C.c_void_p), ("scales", C.c_void_p),
@@ -119,6 +124,7 @@ _SIGS = {
     "llmi_debug_gemv_rows": (_I, [C.POINTER(DebugGemvArgs), _I, _P]),
     "llmi_debug_gemv_plan": (_I, [C.POINTER(DebugGemvArgs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "llmi_debug_attn_oproj": (_I, [C.POINTER(DebugAttnOprojArgs), _P]),
+    "llmi_debug_attn_oproj_rows": (_I, [C.POINTER(DebugAttnOprojArgs), _I, _P]),
     "llmi_debug_prefill_stamps": (_I, [_P]),
     "llmi_debug_prefill_attn": (_I, [C.POINTER(DebugPrefillAttnArgs), _P]),
     "llmi_debug_prefill_attn_plan": (_I, [C.POINTER(DebugPrefillAttnArgs), C.POINTER(_I), C.POINTER(_I),
@@ -157,6 +163,10 @@ _SIGS = {
     "llmi_engine_load_tensor_quantized": (_I, [_P, C.c_char_p, _P, _SZ]),
     "llmi_engine_set_prompt": (_I, [_P, _P, _I]),
     "llmi_engine_decode": (_I, [_P, _I, _I]),
+    "llmi_engine_set_speculation": (_I, [_P, _I]),
+    "llmi_engine_verify": (_I, [_P, _P, _I, _I, C.POINTER(_I)]),
+    "llmi_lookup_draft": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(_I)]),
+    "llmi_engine_generate_lookup": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(SpecStats)]),
     "llmi_engine_prefill": (_I, [_P, _I, _I]),
     "llmi_engine_prefill_scored": (_I, [_P, _I, _I]),
     "llmi_engine_scored_logits": (_I, [_P, _I, _P, _I]),

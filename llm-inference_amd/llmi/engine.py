@@ -36,6 +36,18 @@ def synth_prompt(seed: int, n: int, vocab: int) -> np.ndarray:
     return out
 
 
+def lookup_draft(ids, ngram_max: int = 3, ngram_min: int = 1, max_draft: int = 7) -> np.ndarray:
+    """Prompt-lookup draft (llmi_lookup_draft, on the host): the ids that followed the most
+    recent earlier occurrence of the sequence's longest matching suffix (ngram_max down to
+    ngram_min ids), at most max_draft of them; empty when nothing matches."""
+    ids = np.ascontiguousarray(ids, dtype=np.int32)
+    out = np.zeros(8, np.int32)
+    n = C.c_int()
+    call("llmi_lookup_draft", ids.ctypes.data, len(ids), int(ngram_max), int(ngram_min), int(max_draft),
+         out.ctypes.data, C.byref(n))
+    return out[:n.value].copy()
+
+
 def _read_logprobs(fn: str, handle: tuple, n: int):
     """The records of llmi_engine_logprobs / llmi_batch_logprobs as numpy arrays."""
     valid, top = C.c_int(), C.c_int()
@@ -254,12 +266,48 @@ class Engine:
         call("llmi_engine_time_kernel", self._h, self.KERNELS[which], iters, C.byref(us), C.byref(b))
         return us.value, b.value
 
+    def set_speculation(self, max_draft: int):
+        """Speculative decoding (llmi_engine_set_speculation): allocate lanes for up to max_draft
+        (0..7) proposed tokens per verify step; 0 turns it off. Raises LlmiError where the
+        configuration has no verify step (TP, int4 weights, an int8 KV cache, the ring mode, a
+        sampler, logprobs)."""
+        call("llmi_engine_set_speculation", self._h, int(max_draft))
+
+    def verify(self, draft, use_graph: bool = True) -> int:
+        """One verify step (llmi_engine_verify): the pending token and the proposed continuation
+        `draft` run through the model in one pass; returns how many draft ids were accepted (a).
+        The engine is then exactly where a + 1 decode steps would have left it."""
+        d = np.ascontiguousarray(draft, dtype=np.int32)
+        a = C.c_int()
+        call("llmi_engine_verify", self._h, d.ctypes.data if len(d) else None, len(d), 1 if use_graph else 0,
+             C.byref(a))
+        return a.value
+
+    def generate_lookup(self, n_steps: int, max_draft: int, ngram=(3, 1), use_graph: bool = True):
+        """llmi_engine_generate_lookup: advance exactly n_steps positions with prompt-lookup drafts
+        (ngram = (max, min) suffix lengths); returns the counts (llmi_spec_stats: verify_steps,
+        drafted, accepted)."""
+        st = _lib.SpecStats()
+        call("llmi_engine_generate_lookup", self._h, int(n_steps), int(max_draft), int(ngram[0]), int(ngram[1]),
+             1 if use_graph else 0, C.byref(st))
+        return st
+
     def generate(self, prompt, n_new: int, use_graph: bool = True, prefill: bool = False,
-                 exact: bool = True) -> np.ndarray:
+                 exact: bool = True, speculate: int = 0, ngram=(3, 1)) -> np.ndarray:
         """Greedy: feed the prompt, produce n_new tokens (Llama<T>::Response).
-        prefill=True runs the prompt as one batched pass (firstTokenGen)."""
+        prefill=True runs the prompt as one batched pass (firstTokenGen). speculate=k (1..7):
+        after the prompt, the n_new - 1 steps run as verify steps over prompt-lookup drafts of
+        up to k ids (the same tokens, bit for bit); the counts are left in self.spec_stats."""
         prompt = np.asarray(prompt, np.int32)
         self.set_prompt(prompt)
+        if speculate:
+            self.set_speculation(speculate)
+            if prefill:
+                self.prefill(len(prompt), exact)
+            else:
+                self.decode(len(prompt), use_graph)
+            self.spec_stats = self.generate_lookup(n_new - 1, speculate, ngram, use_graph)
+            return self.tokens(len(prompt) + n_new)[len(prompt):]
         if prefill:
             self.prefill(len(prompt), exact)
             self.decode(n_new - 1, use_graph)

@@ -529,6 +529,20 @@ def debug_attn_oproj(**fields) -> None:
     call("llmi_debug_attn_oproj", ctypes.byref(a), _stream())
 
 
+def attn_oproj_rows(rows) -> None:
+    """llmi_debug_attn_oproj_rows (test hook): ONE multi-row attention launch and ONE multi-row
+    o_proj launch for the query rows in `rows`, a list of debug_attn_oproj keyword dicts that
+    share the caches, shapes, rope, W_o, nact and err and differ in qkv, workspace, xacc and the
+    residual seed. Row i sits at position *rows[0]["pos_dev"] + i; its xacc, partials and cache
+    row are bitwise debug_attn_oproj(**rows[i])'s at that position, the rows run in order."""
+    arr = (_lib.DebugAttnOprojArgs * max(len(rows), 1))()
+    for i, fields in enumerate(rows):
+        fields = dict(fields)
+        fields.setdefault("resid_scale", 1.0)
+        arr[i] = _debug_args(_lib.DebugAttnOprojArgs, fields)
+    call("llmi_debug_attn_oproj_rows", arr, len(rows), _stream())
+
+
 def debug_prefill_attn(**fields) -> None:
     """llmi_debug_prefill_attn (test hook): one launch of the prefill attention (rope + cache
     write, attention, merge) with llmi_debug_prefill_attn_args filled from the keywords
