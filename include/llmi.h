@@ -460,6 +460,39 @@ int llmi_logprobs(const float* logits, int rows, int vocab, const int32_t* ids /
                   float* out_lp /* [rows] */, int32_t* top_ids /* [rows, n_top] */, float* top_lp /* [rows, n_top] */,
                   float* out_lse /* [rows], nullable */, llmi_stream_t stream);
 
+/* Logit rules over whole rows of logits [rows, vocab] (f32, not modified): an additive bias, the
+ * presence and frequency penalties over a history of ids, and an allowed-token bitmap. No
+ * reference counterpart; the rule is specified in DESIGN.md ("Logit rules") and restated in
+ * tests/logit_rules_ref.py. For id i, in this order, every step one round-to-nearest fp32
+ * operation with no contraction:
+ *   1. v = z[i]; NaN counts as -inf (llmi_sample_nucleus's convention);
+ *   2. bias (nullable dense row [vocab], shared by the rows): if bias[i] != 0, v = v + bias[i]
+ *      (bias[i] finite, or -inf: a ban; a zero of either sign leaves v's bits alone);
+ *   3. c = the occurrences of i in the row's history; if c > 0 and a penalty is non-zero:
+ *      t = frequency * (float)c; t = presence + t; v = v - t (the OpenAI / vLLM rule);
+ *      a NaN that steps 2 and 3 produce (+inf meeting -inf) counts as -inf;
+ *   4. allowed (nullable bitmap): bit i & 31 of word i >> 5 clear -> v = -inf. allowed_stride is
+ *      in words: 0 = one bitmap of (vocab + 31) / 32 words for all rows, else row r's bitmap
+ *      starts at word r * allowed_stride (>= (vocab + 31) / 32). Bits at or above vocab are ignored.
+ * out [rows, vocab] receives the processed rows (out must not be logits) and out_ids [rows] the
+ * argmax of each processed row in llmi_argmax's order (value descending, ties to the lower id;
+ * a row of only -inf gives id 0). With no bias, no bitmap and zero penalties the processed row
+ * is bitwise the raw row, NaN aside. Every count is an integer and every id's value is
+ * computed from its own inputs alone, so the result has the same bits in any launch.
+ * history [rows, history_stride] device int32 with history_len[row] valid ids per row
+ * (history_len NULL: no history). rows <= 65536; vocab <= 131072 and history_stride <= 65535
+ * (LLMI_EUNSUPPORTED above: 16-bit counters). LLMI_EINVAL: null logits / out / out_ids, out ==
+ * logits, a penalty that is not finite, a bad allowed_stride, history_len without a history, a
+ * bias value that is NaN or +inf, history_len outside [0, history_stride], history ids outside
+ * [0, vocab) (the last three are read back and checked unless the stream is being captured;
+ * the kernel clamps the length and ignores such ids). One launch, one workgroup per row;
+ * graph-capturable; allocates nothing. */
+int llmi_process_logits(const float* logits, int rows, int vocab, const float* bias /* [vocab], nullable */,
+                        const uint32_t* allowed /* nullable */, int allowed_stride, const int32_t* history,
+                        int history_stride, const int32_t* history_len /* [rows], NULL: none */,
+                        float presence_penalty, float frequency_penalty, float* out /* [rows, vocab] */,
+                        int32_t* out_ids /* [rows] */, llmi_stream_t stream);
+
 /* The draw llmi_sampling makes, computed on the host (no device work): the first
  * curand_uniform of curand_init(seed, subsequence, 0) -- cuRAND's XORWOW as restated in
  * csrc/xorwow.h (subsequence < 65536). For checking the restatement against a CPU oracle. */

@@ -505,6 +505,14 @@ int llmi_sample_nucleus(const float* logits, int rows, int vocab, const int32_t*
                                  temperature, top_k, top_p, step, out_id, out_kept, STREAM(stream));
 }
 
+int llmi_process_logits(const float* logits, int rows, int vocab, const float* bias, const uint32_t* allowed,
+                        int allowed_stride, const int32_t* history, int history_stride, const int32_t* history_len,
+                        float presence_penalty, float frequency_penalty, float* out, int32_t* out_ids,
+                        llmi_stream_t stream) {
+    return logit_rules_launch(logits, rows, vocab, bias, allowed, allowed_stride, history, history_stride, history_len,
+                              presence_penalty, frequency_penalty, out, out_ids, STREAM(stream));
+}
+
 int llmi_logprobs(const float* logits, int rows, int vocab, const int32_t* ids, int n_top, float* out_lp,
                   int32_t* top_ids, float* top_lp, float* out_lse, llmi_stream_t stream) {
     return logprobs_launch(logits, rows, vocab, ids, n_top, out_lp, top_ids, top_lp, out_lse, STREAM(stream));

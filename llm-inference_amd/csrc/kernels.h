@@ -575,6 +575,12 @@ int engine_logprob_launch(const struct DecodeState* st, const float* logits, int
 // id outside [0, vocab) scores id 0). The ids are the engine's own: no host check, no sync.
 int engine_logprob_rows_launch(const float* slab, int rows, int vocab, const int32_t* prompt, int rec0, int max_seq,
                                int n_top, float* tok_lp, int32_t* top_ids, float* top_lp, hipStream_t s);
+// logit rules over whole rows (logit_rules.hip): bias (nullable dense row, -inf bans), presence /
+// frequency penalties over a history, an allowed bitmap (nullable; allowed_stride words per row,
+// 0: one for all rows) -> the processed rows in `out` (never the input) and their argmax ids
+int logit_rules_launch(const float* logits, int rows, int vocab, const float* bias, const uint32_t* allowed,
+                       int allowed_stride, const int32_t* history, int history_stride, const int32_t* history_len,
+                       float presence, float frequency, float* out, int32_t* out_ids, hipStream_t s);
 int repeat_kv_launch(const void* k_cache, const void* v_cache, int dtype, int layer, const int* ctx_len, int batch,
                      int kv_heads, int max_seq, int heads, int max_k_len, int d, void* k_dst, void* v_dst,
                      hipStream_t s);

@@ -104,6 +104,7 @@ _SIGS = {
     "llmi_sampling": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     "llmi_sample_nucleus": (_I, [_P, _I, _I, _P, _I, _P, _F, _F, _I, _F, _U64, _P, _P, _P]),
     "llmi_logprobs": (_I, [_P, _I, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "llmi_process_logits": (_I, [_P, _I, _I, _P, _P, _I, _P, _I, _P, _F, _F, _P, _P, _P]),
     "llmi_repeat_kv": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
     "llmi_padding_offset": (_I, [_P, _P, _P, _I, _I, _P]),
     "llmi_rope_qkv_prefill": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),

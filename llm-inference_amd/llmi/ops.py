@@ -194,6 +194,51 @@ def sample_nucleus(logits: torch.Tensor, step: int, top_k: int = 0, top_p: float
     return out_id, out_kept
 
 
+def process_logits(logits: torch.Tensor, bias: torch.Tensor = None, allowed: torch.Tensor = None,
+                   history: torch.Tensor = None, history_len: torch.Tensor = None, presence_penalty: float = 0.0,
+                   frequency_penalty: float = 0.0, out: torch.Tensor = None, out_ids: torch.Tensor = None):
+    """llmi_process_logits (no reference counterpart): logits [rows, vocab] (or [vocab]) fp32,
+    left unchanged; bias fp32 [vocab] (finite or -inf), shared by the rows; allowed an int32
+    bitmap (the uint32 words' bits) of (vocab + 31) // 32 words, [words] for all rows or
+    [rows, words]; history [rows, n] int32 with history_len [rows] valid ids per row (None: all
+    n). Returns (out, out_ids): the processed rows fp32 [rows, vocab] and their argmax int32
+    [rows] (value descending, ties to the lower id)."""
+    _dev(logits, bias, allowed, history, history_len, out, out_ids)
+    if logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise ValueError("process_logits: logits must be contiguous float32")
+    x = logits.view(-1, logits.shape[-1])
+    rows, vocab = x.shape
+    words = (vocab + 31) // 32
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != vocab):
+        raise ValueError("process_logits: bias must be contiguous float32 [vocab]")
+    a_stride = 0
+    if allowed is not None:
+        if allowed.dtype != torch.int32 or not allowed.is_contiguous() or allowed.numel() not in (words, rows * words):
+            raise ValueError("process_logits: allowed must be contiguous int32 [words] or [rows, words]")
+        a_stride = words if (allowed.dim() == 2 and allowed.shape[0] == rows) else 0
+    h_stride = 0
+    if history is not None:
+        if history.dtype != torch.int32 or not history.is_contiguous():
+            raise ValueError("process_logits: history must be contiguous int32")
+        history = history.view(rows, -1)
+        h_stride = history.shape[1]
+        if history_len is None:
+            history_len = torch.full((rows,), h_stride, device=x.device, dtype=torch.int32)
+    for t in (history_len, out_ids):
+        if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() != rows):
+            raise ValueError("process_logits: history_len and out_ids must be contiguous int32 [rows]")
+    if out is not None and (out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != x.numel()):
+        raise ValueError("process_logits: out must be contiguous float32 [rows, vocab]")
+    if out is None:
+        out = torch.empty_like(x)
+    if out_ids is None:
+        out_ids = torch.empty(rows, device=x.device, dtype=torch.int32)
+    call("llmi_process_logits", x.data_ptr(), rows, vocab, _p(bias), _p(allowed), a_stride, _p(history), h_stride,
+         _p(history_len), float(presence_penalty), float(frequency_penalty), out.data_ptr(), out_ids.data_ptr(),
+         _stream())
+    return out.view(rows, vocab), out_ids
+
+
 def logprobs(logits: torch.Tensor, ids: torch.Tensor = None, n_top: int = 0):
     """llmi_logprobs (no reference counterpart): logits [rows, vocab] (or [vocab]) fp32, left
     unchanged and taken raw (no penalty, no temperature); ids int32 [rows] (None: none scored).
