@@ -836,6 +836,60 @@ typedef struct llmi_spec_stats {
 } llmi_spec_stats;
 int llmi_engine_generate_lookup(llmi_engine* e, int n_steps, int max_draft, int ngram_max, int ngram_min,
                                 int use_graph, llmi_spec_stats* stats);
+/* Edit a sequence in place (no reference counterpart): keep a prefix, force what follows. With P
+ * the engine's next position (positions 0 .. P - 1 consumed; a pending token for P exists once
+ * the prompt is used up), llmi_engine_edit(e, keep, ids, n) leaves positions 0 .. keep - 1
+ * consumed, forgets the old pending token and everything at or after keep, and makes positions
+ * keep .. keep + n - 1 take ids as a prompt would: afterwards the next position is keep and the
+ * prompt length keep + n, and llmi_engine_decode, llmi_engine_prefill (from keep),
+ * llmi_engine_verify and the samplers go on from there -- bitwise as an engine that was given
+ * the kept ids + ids as its prompt. It rewinds a continuation, appends a turn without feeding
+ * the history again (keep = P, ids = the pending token, then the turn), and gives a draft engine
+ * the token its target chose.
+ *   Needs a prompt set, 0 <= keep <= P, n >= 0, keep + n <= max_seq, every id in [0, vocab), and
+ * n >= 1 unless keep == P (keep == P with n == 0 does nothing, the pending token included); each
+ * violation returns LLMI_EINVAL and changes nothing. Allowed wherever llmi_engine_set_prompt is,
+ * speculating engines included (the lanes are not touched); the ring decode mode returns
+ * LLMI_EUNSUPPORTED.
+ *   One stream-ordered launch (seq_edit_kernel) writes the device positions, ids into the prompt
+ * buffer and the logprob records; for n <= 8 the ids travel in the launch arguments and the call
+ * neither copies nor synchronises, a longer list is copied first and the call synchronises (as
+ * llmi_engine_set_prompt). Nothing is cleared: cache rows at or after keep are stale and are
+ * overwritten before any attention reads them (as a verify step's rejected rows); the device
+ * error word and the forward counter are left alone; the captured step graphs stay valid.
+ * Logprob records q >= keep become "not computed" (NaN / id -1) and records below keep keep
+ * their bits; record keep itself STAYS not computed, because the forward at keep - 1 that would
+ * write it is not run again. The scored-prefill slab is forgotten (llmi_engine_scored_logits).
+ *
+ * llmi_engine_position: the next position and the prompt length as the host tracks them (each
+ * nullable); no synchronisation. */
+int llmi_engine_edit(llmi_engine* e, int keep, const int32_t* ids, int n);
+int llmi_engine_position(llmi_engine* e, int* next_pos, int* prompt_len);
+/* Greedy generation with a second engine as the proposer (draft-model speculative decoding):
+ * advances `target` by exactly n_steps positions and leaves it in bitwise the state
+ * llmi_engine_decode(target, n_steps, .) leaves it in -- tokens, logits, hidden state and cache
+ * -- WHATEVER the draft proposes; only the number of verify steps depends on the draft.
+ *   The target: as llmi_engine_generate_lookup (prompt consumed, max_draft <=
+ * llmi_engine_set_speculation's, LLMI_EINVAL), and nothing llmi_engine_set_speculation refuses
+ * may be active (LLMI_EUNSUPPORTED). The draft: any single-rank engine in decode mode 0 on the
+ * same device with the same vocab and max_seq >= the target's, not the target itself
+ * (LLMI_EINVAL); its shape, seed, weight dtype (int4 included), KV dtype (int8 included) and
+ * sampler are free: it only ever runs plain token steps.
+ *   Host loop. Catch-up: the target's sequence is read once (pending token included); the draft
+ * keeps the longest prefix it has already consumed with the same ids (none for a draft without
+ * a prompt), is edited to the rest (llmi_engine_edit) and runs all but the last forced position
+ * -- through its prefill (fp32-faithful planes) when draft_prefill != 0, more than one row is
+ * missing and it has one (not int4), as decode steps otherwise. A cycle at target position p:
+ * k = min(max_draft, remaining - 1, max_seq - p - 1); the draft steps until it holds k ids
+ * beyond p (k steps, plus one per forced id it has not consumed); its tokens p + 1 .. p + k are
+ * read back (k ids and the draft's error word) and verified (llmi_engine_verify: a accepted,
+ * next token g); the draft is edited to keep = min(p + a + 1, p + k) with the target's tokens
+ * keep .. p + a + 1 -- one id, or two when every proposal was accepted -- which travel in the
+ * launch arguments, so the draft adds one synchronisation a cycle (the read-back).
+ * stats (nullable) as llmi_engine_generate_lookup. The draft is left aligned with the target:
+ * a second call finds nothing to catch up. */
+int llmi_engine_generate_draft(llmi_engine* target, llmi_engine* draft, int n_steps, int max_draft,
+                               int draft_prefill, int use_graph, llmi_spec_stats* stats);
 /* Prefill (Llama<T>::firstTokenGen, llama.cpp:273-316; LlamaContextDecoder::forward,
  * context_decoder.cpp:47-143): the next n_tokens prompt rows in one batched pass
  * (chunks of 512) -- MFMA GEMMs, causal prefill attention, KV slots written --
@@ -1018,6 +1072,10 @@ int llmi_batch_load_bin(llmi_batch* b, const char* weight_path);
 int llmi_batch_load_bin_quantized(llmi_batch* b, const char* weight_path);
 int llmi_batch_set_prompt(llmi_batch* b, int seq, const int32_t* ids, int n);
 int llmi_batch_reset(llmi_batch* b, int seq);
+/* llmi_engine_edit of slot seq's sequence, on the batch's stream: the slot goes on bitwise as
+ * the edited engine would alone, the other slots as if nothing happened. LLMI_EINVAL for a seq
+ * out of range, an idle slot, and llmi_engine_edit's own. */
+int llmi_batch_edit(llmi_batch* b, int seq, int keep, const int32_t* ids, int n);
 /* llmi_engine_set_sampling_params for one slot: step = seed + the sampled token's position,
  * row 0, as in the engine. */
 int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_params* p);

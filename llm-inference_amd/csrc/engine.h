@@ -34,8 +34,9 @@
 //
 // One struct Engine, defined over several units: engine_weights.hip (setup and the
 // loaders), engine.hip (the token step, the TP exchange, the ring layer, the setters),
-// engine_prefill.hip, engine_group.hip / engine_batch.hip (Group, Batch),
-// engine_capi.hip (the C ABI) and engine_time.hip (llmi_engine_time_kernel).
+// engine_prefill.hip, engine_spec.hip (the verify step, the lookup and draft-engine loops),
+// engine_edit.hip (rewind / extend a sequence), engine_group.hip / engine_batch.hip (Group,
+// Batch), engine_capi.hip (the C ABI) and engine_time.hip (llmi_engine_time_kernel).
 #pragma once
 #include <rccl/rccl.h>
 
@@ -428,6 +429,14 @@ struct Engine {
     int verify(const int32_t* draft, int n_draft, int use_graph, int* n_accepted, int* next_token = nullptr);
     int generate_lookup(int n_steps, int max_draft, int ngram_max, int ngram_min, int use_graph,
                         llmi_spec_stats* stats);
+    // ... a second engine proposes (this one is the target)
+    int read_ids(int from, int n, int32_t* out);
+    int draft_catch_up(const int32_t* hist, int p, int use_prefill, int use_graph);
+    int generate_draft(Engine& draft, int n_steps, int max_draft, int draft_prefill, int use_graph,
+                       llmi_spec_stats* stats);
+
+    // ---- engine_edit.hip: keep a prefix of the sequence, force the ids that follow
+    int edit(int keep, const int32_t* ids, int n);
 };
 // prompt-lookup drafting on the host (llmi_lookup_draft)
 int lookup_draft(const int32_t* ids, int n, int ngram_max, int ngram_min, int max_draft, int32_t* out, int* n_out);

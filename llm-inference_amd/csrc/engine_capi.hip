@@ -190,6 +190,26 @@ int llmi_engine_generate_lookup(llmi_engine* e, int n_steps, int max_draft, int 
     return e->e.generate_lookup(n_steps, max_draft, ngram_max, ngram_min, use_graph, stats);
 }
 
+int llmi_engine_generate_draft(llmi_engine* target, llmi_engine* draft, int n_steps, int max_draft,
+                               int draft_prefill, int use_graph, llmi_spec_stats* stats) {
+    LLMI_REQUIRE(target && draft, "engine_generate_draft: null engine");
+    LLMI_HIP(hipSetDevice(target->e.device));
+    return target->e.generate_draft(draft->e, n_steps, max_draft, draft_prefill, use_graph, stats);
+}
+
+int llmi_engine_edit(llmi_engine* e, int keep, const int32_t* ids, int n) {
+    LLMI_REQUIRE(e, "engine_edit: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.edit(keep, ids, n);
+}
+
+int llmi_engine_position(llmi_engine* e, int* next_pos, int* prompt_len) {
+    LLMI_REQUIRE(e, "engine_position: null engine");
+    if (next_pos) *next_pos = e->e.host_next_pos;
+    if (prompt_len) *prompt_len = e->e.prompt_len;
+    return LLMI_OK;
+}
+
 int llmi_engine_prefill(llmi_engine* e, int n_tokens, int exact) {
     LLMI_REQUIRE(e, "null engine");
     LLMI_REQUIRE(exact >= 0 && exact <= 2, "prefill: exact must be 0 (fp16 A), 1 (fp32-faithful) or 2 (fp8 lo planes)");
@@ -531,6 +551,13 @@ int llmi_batch_set_prompt(llmi_batch* b, int seq, const int32_t* ids, int n) {
     LLMI_TRY(b->b.slot_ok(seq));
     LLMI_HIP(hipSetDevice(b->b.r[0]->device));
     return b->b.r[seq]->set_prompt(ids, n);
+}
+
+int llmi_batch_edit(llmi_batch* b, int seq, int keep, const int32_t* ids, int n) {
+    LLMI_REQUIRE(b, "batch_edit: null batch");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    return b->b.r[seq]->edit(keep, ids, n);  // (an idle slot has no prompt: LLMI_EINVAL)
 }
 
 int llmi_batch_reset(llmi_batch* b, int seq) {

@@ -13,6 +13,10 @@
 // launch gives row i bitwise its single-row result (gemv_rows.hip, attn_rows.hip) and the
 // residual stream is integer fixed point, so row i's logits are bitwise those of the plain
 // step at position p + i after the same tokens: what is accepted is exactly greedy decode.
+//
+// Proposals come from a host lookup in the sequence itself (generate_lookup) or from a second,
+// smaller engine that runs plain token steps and is re-aligned after every verify step with
+// Engine::edit (generate_draft); the target's result does not depend on what is proposed.
 #include "engine.h"
 
 namespace llmi {
@@ -374,6 +378,93 @@ int Engine::generate_lookup(int n_steps, int max_draft, int ngram_max, int ngram
         hist[p + a + 1] = next;
         st_.verify_steps += 1;
         st_.drafted += nd;
+        st_.accepted += a;
+        remaining -= a + 1;
+    }
+    if (stats) *stats = st_;
+    return LLMI_OK;
+}
+
+// ------------------------------------------------------------ a draft engine proposes
+// tokens[from .. from + n) read back narrowly (the pending token is finalized first), with the
+// device error word: all a draft loop ever reads of an engine
+int Engine::read_ids(int from, int n, int32_t* out) {
+    if (host_next_pos >= prompt_len && host_next_pos <= c.max_seq)
+        LLMI_TRY(finalize_launch(st, partials, lm_grid, tokens, c.max_seq, stream));
+    LLMI_HIP(hipStreamSynchronize(stream));
+    int err = 0;
+    LLMI_HIP(hipMemcpy(&err, &st->error, sizeof(int), hipMemcpyDeviceToHost));
+    LLMI_REQUIRE(err == 0, "generate_draft: the draft's device error flag " + std::to_string(err));
+    LLMI_REQUIRE(from >= 0 && n >= 0 && from + n <= c.max_seq + 1, "generate_draft: ids out of range");
+    if (n > 0) LLMI_HIP(hipMemcpy(out, tokens + from, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return LLMI_OK;
+}
+
+// This (draft) engine takes the target's sequence hist[0 .. p] (p: the target's next position,
+// hist[p] its pending token): the longest prefix it has already consumed with the same ids is
+// kept, the rest forced, and every forced position but p run -- next position p afterwards.
+int Engine::draft_catch_up(const int32_t* hist, int p, int use_prefill, int use_graph) {
+    int m = 0;
+    if (prompt_len > 0) {
+        const int have = std::min(host_next_pos, p);  // (position p is always forced)
+        std::vector<int32_t> own((size_t)have);
+        if (have > 0) LLMI_TRY(read_ids(0, have, own.data()));
+        while (m < have && own[m] == hist[m]) ++m;
+        LLMI_TRY(edit(m, hist + m, p + 1 - m));
+    } else {
+        LLMI_TRY(set_prompt(hist, p + 1));
+    }
+    const int rows = p - m;
+    if (rows == 0) return LLMI_OK;
+    if (use_prefill && rows > 1 && wdt != LLMI_I4) return prefill(rows, 2);
+    return decode(rows, use_graph);
+}
+
+int Engine::generate_draft(Engine& d, int n_steps, int max_draft, int draft_prefill, int use_graph,
+                           llmi_spec_stats* stats) {
+    LLMI_REQUIRE(n_steps >= 0, "generate_draft: n_steps must be >= 0");
+    LLMI_REQUIRE(&d != this, "generate_draft: the draft is the target itself");
+    LLMI_REQUIRE(d.c.tp_world == 1 && !d.grouped && !d.kv_from, "generate_draft: the draft must be a single-rank engine");
+    LLMI_REQUIRE(d.decode_mode == 0, "generate_draft: the draft runs decode mode 0 (the ring mode has no edit)");
+    LLMI_REQUIRE(d.c.vocab == c.vocab, "generate_draft: the draft's vocab differs from the target's");
+    LLMI_REQUIRE(d.device == device, "generate_draft: the draft is on another device");
+    LLMI_REQUIRE(d.c.max_seq >= c.max_seq, "generate_draft: the draft's max_seq is smaller than the target's");
+    if (const char* why = spec_refusal()) {
+        set_last_error(std::string("[llmi][ERROR] generate_draft: the target: ") + why);
+        return LLMI_EUNSUPPORTED;
+    }
+    LLMI_REQUIRE(max_draft >= 0 && max_draft <= spec_max, "generate_draft: max_draft must be in [0, set_speculation's]");
+    LLMI_REQUIRE(prompt_len > 0 && host_next_pos >= prompt_len, "generate_draft: the target's prompt is not consumed yet");
+    LLMI_REQUIRE(host_next_pos + n_steps <= c.max_seq, "generate_draft: would run past max_seq");
+    llmi_spec_stats st_{0, 0, 0};
+    if (stats) *stats = st_;
+    if (n_steps == 0) return LLMI_OK;
+    // the target's sequence and its pending token (position host_next_pos), read once
+    std::vector<int32_t> hist((size_t)c.max_seq + 1);
+    int valid = 0;
+    LLMI_TRY(tokens_out(hist.data(), c.max_seq + 1, &valid));
+    LLMI_REQUIRE(valid == host_next_pos + 1, "generate_draft: the token history is short");
+    LLMI_TRY(d.draft_catch_up(hist.data(), host_next_pos, draft_prefill, use_graph));
+    int remaining = n_steps;
+    while (remaining > 0) {
+        const int p = host_next_pos;
+        const int k = std::max(0, std::min(std::min(max_draft, remaining - 1), c.max_seq - p - 1));
+        int32_t prop[kAttnRowsMax];
+        if (k > 0) {  // the forced ids it has not consumed yet, then k - 1 of its own: ids p + 1 .. p + k
+            LLMI_TRY(d.decode(p + k - d.host_next_pos, use_graph));
+            LLMI_TRY(d.read_ids(p + 1, k, prop));
+        }
+        int a = 0, next = 0;
+        LLMI_TRY(verify(prop, k, use_graph, &a, &next));
+        for (int j = 0; j < a; ++j) hist[p + 1 + j] = prop[j];
+        hist[p + a + 1] = next;
+        // the draft drops what was rejected and takes the target's token: one id, or two when
+        // every proposal was accepted (its own pending id, now consumed by the target, and g)
+        const int last = std::min(p + a + 1, d.c.max_seq - 1);
+        const int keep = std::min(last, d.host_next_pos);
+        LLMI_TRY(d.edit(keep, hist.data() + keep, last - keep + 1));
+        st_.verify_steps += 1;
+        st_.drafted += k;
         st_.accepted += a;
         remaining -= a + 1;
     }

@@ -168,6 +168,10 @@ _SIGS = {
     "llmi_engine_verify": (_I, [_P, _P, _I, _I, C.POINTER(_I)]),
     "llmi_lookup_draft": (_I, [_P, _I, _I, _I, _I, _P, C.POINTER(_I)]),
     "llmi_engine_generate_lookup": (_I, [_P, _I, _I, _I, _I, _I, C.POINTER(SpecStats)]),
+    "llmi_engine_generate_draft": (_I, [_P, _P, _I, _I, _I, _I, C.POINTER(SpecStats)]),
+    "llmi_engine_edit": (_I, [_P, _I, _P, _I]),
+    "llmi_engine_position": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "llmi_batch_edit": (_I, [_P, _I, _I, _P, _I]),
     "llmi_engine_prefill": (_I, [_P, _I, _I]),
     "llmi_engine_prefill_scored": (_I, [_P, _I, _I]),
     "llmi_engine_scored_logits": (_I, [_P, _I, _P, _I]),

@@ -292,12 +292,45 @@ class Engine:
              1 if use_graph else 0, C.byref(st))
         return st
 
+    def generate_draft(self, draft: "Engine", n_steps: int, max_draft: int, prefill: bool = False,
+                       use_graph: bool = True):
+        """llmi_engine_generate_draft: advance exactly n_steps positions with the engine `draft`
+        proposing up to max_draft ids a verify step (prefill: the draft catches up on the sequence
+        so far through its prefill where it has one); the tokens are plain greedy decode's bit for
+        bit whatever the draft proposes. Returns the counts (llmi_spec_stats)."""
+        st = _lib.SpecStats()
+        call("llmi_engine_generate_draft", self._h, draft._h, int(n_steps), int(max_draft), 1 if prefill else 0,
+             1 if use_graph else 0, C.byref(st))
+        return st
+
+    def edit(self, keep: int, ids):
+        """llmi_engine_edit: keep positions 0 .. keep - 1, forget the pending token and everything
+        after them, and force `ids` on the positions that follow (as a prompt would)."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        call("llmi_engine_edit", self._h, int(keep), ids.ctypes.data if len(ids) else None, len(ids))
+
+    def position(self):
+        """(next position, prompt length) as the host tracks them (llmi_engine_position; no sync)."""
+        p, n = C.c_int(), C.c_int()
+        call("llmi_engine_position", self._h, C.byref(p), C.byref(n))
+        return p.value, n.value
+
+    def extend(self, ids):
+        """Append `ids` after the whole text so far (the pending token included): a new turn
+        without feeding the history again. edit(P, [pending] + ids); needs the prompt consumed."""
+        p, n = self.position()
+        if n == 0 or p < n:
+            raise _lib.LlmiError("extend: the prompt is not consumed yet (decode or prefill it first)")
+        pending = self.tokens(p + 1)[p:]
+        self.edit(p, np.concatenate([pending, np.asarray(ids, np.int32).reshape(-1)]))
+
     def generate(self, prompt, n_new: int, use_graph: bool = True, prefill: bool = False,
-                 exact: bool = True, speculate: int = 0, ngram=(3, 1)) -> np.ndarray:
+                 exact: bool = True, speculate: int = 0, ngram=(3, 1), draft: Optional["Engine"] = None) -> np.ndarray:
         """Greedy: feed the prompt, produce n_new tokens (Llama<T>::Response).
         prefill=True runs the prompt as one batched pass (firstTokenGen). speculate=k (1..7):
         after the prompt, the n_new - 1 steps run as verify steps over prompt-lookup drafts of
-        up to k ids (the same tokens, bit for bit); the counts are left in self.spec_stats."""
+        up to k ids, or -- draft=another Engine -- over that engine's proposals (the same
+        tokens, bit for bit); the counts are left in self.spec_stats."""
         prompt = np.asarray(prompt, np.int32)
         self.set_prompt(prompt)
         if speculate:
@@ -306,7 +339,10 @@ class Engine:
                 self.prefill(len(prompt), exact)
             else:
                 self.decode(len(prompt), use_graph)
-            self.spec_stats = self.generate_lookup(n_new - 1, speculate, ngram, use_graph)
+            if draft is not None:
+                self.spec_stats = self.generate_draft(draft, n_new - 1, speculate, prefill, use_graph)
+            else:
+                self.spec_stats = self.generate_lookup(n_new - 1, speculate, ngram, use_graph)
             return self.tokens(len(prompt) + n_new)[len(prompt):]
         if prefill:
             self.prefill(len(prompt), exact)
@@ -430,6 +466,13 @@ class Batch:
         """Make slot seq idle (its buffers keep their contents)."""
         call("llmi_batch_reset", self._h, int(seq))
         self._plen[int(seq)], self._pos[int(seq)] = 0, 0
+
+    def edit(self, seq: int, keep: int, ids):
+        """Engine.edit for one slot (llmi_batch_edit); the other slots are left where they are."""
+        ids = np.ascontiguousarray(ids, dtype=np.int32)
+        call("llmi_batch_edit", self._h, int(seq), int(keep), ids.ctypes.data if len(ids) else None, len(ids))
+        if len(ids):
+            self._plen[int(seq)], self._pos[int(seq)] = int(keep) + len(ids), int(keep)
 
     def prefill(self, seq: int, n: Optional[int] = None, exact=True, score: bool = False):
         """Engine.prefill for one slot (llmi_batch_prefill): its next n prompt rows (None: the
