@@ -323,6 +323,46 @@ int llmi_debug_prefill_attn(const llmi_debug_prefill_attn_args* args, llmi_strea
 int llmi_debug_prefill_attn_plan(const llmi_debug_prefill_attn_args* args, int* cb, int* maxc, int* grid,
                                  int* merge_slots);
 
+/* llmi_debug_gemm: one launch of a prefill GEMM, Y (op)= sum_p A_p W^T, with the launcher's
+ * argument block (Gemm2Args) filled field for field and handed to the production launcher
+ * (test-only: no engine or operator path calls it). kernel 2: gemm2 (64 / 128 x 128 tiles);
+ * 3: gemm3 (256 x 256 tiles). a_hi (, a_lo): fp16 planes [m, lda], planes 1 or 2; w fp16 [n, k].
+ * epi: 0 store, 1 add, 5 slab (y [m, ldy] fp32; slab [ksplit][m][ldy]: slice s holds the sum
+ * over its K range alone), 2 gate_up (w = [gate; up] rows, n = 2 x inter, the pair offset is set
+ * to n / 2: silu(gate) * up into y [m, ldy] fp32 or, with y_hi (, y_lo), as fp16 planes).
+ * lo8 (gemm3, planes 2): a_lo rows of 2 lda bytes whose first lda bytes are e4m3(lo * 2^12),
+ * against w8 (rows of 2 k bytes, the first k = e4m3(W * 2^w8_exp)); gate_up then writes y_lo in
+ * the same byte format. stream_k 1 (gemm3): gemm3_sk_attach first, as the engine's gate_up does
+ * -- stream-K where that function takes it, the plain kernel where it declines; err: the sticky
+ * error word (NULL: the stream's own, llmi_stream_errors). Nothing is allocated or launched on
+ * a refused call. The caller owns every buffer.
+ * llmi_debug_gemm_plan launches and allocates nothing: it runs the launcher's argument checks
+ * and the functions the launchers take their choices from, and reports the row tile (bm: 64 or
+ * 128 for gemm2, 256 for gemm3), the workgroup count, and the stream-K slots per tile (sk_pmax;
+ * 0: the plain kernel -- one plane without lo8, more than 3 slots, or no stream_k). */
+typedef struct llmi_debug_gemm_args {
+    int kernel;
+    const void* a_hi;
+    const void* a_lo;
+    int planes, lda;
+    const void* w;
+    int m, n, k;
+    int epi;
+    float* y;
+    void* y_hi;
+    void* y_lo;
+    int ldy;
+    int ksplit;
+    float* slab;
+    int lo8;
+    const void* w8;
+    int w8_exp;
+    int stream_k;
+    int* err;
+} llmi_debug_gemm_args;
+int llmi_debug_gemm(const llmi_debug_gemm_args* args, llmi_stream_t stream);
+int llmi_debug_gemm_plan(const llmi_debug_gemm_args* args, int* bm, int* grid, int* sk_pmax);
+
 /* llmi_debug_rows_split: the prefill GEMMs' activation producer. Rows of x [m, ldx] (k used):
  * with slab [ksplit][m][k] (ldx == k) x += slice 0 + slice 1 + ... in that order, written
  * back; then optional RMSNorm (gamma [k] of g_dtype f16 / f32; NULL: none); then fp16 planes

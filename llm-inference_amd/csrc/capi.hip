@@ -288,6 +288,58 @@ int llmi_debug_prefill_attn_plan(const llmi_debug_prefill_attn_args* args, int* 
     return LLMI_OK;
 }
 
+namespace {
+// the launcher's argument block from the hook's, and the plan of that launch: the launcher's own
+// checks and choices (gemm2_plan / gemm3_plan), with stream_k the decision gemm3_sk_attach
+// takes (gemm3_sk_decide) -- nothing launched, nothing allocated
+int debug_gemm_plan(const llmi_debug_gemm_args* args, Gemm2Args* g, GemmPlan* p) {
+    LLMI_REQUIRE(args != nullptr, "debug_gemm: null arguments");
+    const llmi_debug_gemm_args& d = *args;
+    LLMI_REQUIRE(d.kernel == 2 || d.kernel == 3, "debug_gemm: kernel must be 2 (gemm2) or 3 (gemm3)");
+    LLMI_REQUIRE(d.stream_k == 0 || (d.stream_k == 1 && d.kernel == 3), "debug_gemm: stream_k is 0 or 1, gemm3 only");
+    LLMI_REQUIRE(d.kernel == 3 || !d.lo8, "debug_gemm: the fp8 lo plane is a gemm3 form");
+    Gemm2Args a;
+    a.a[0] = static_cast<const _Float16*>(d.a_hi); a.a[1] = static_cast<const _Float16*>(d.a_lo);
+    a.planes = d.planes; a.lda = d.lda;
+    a.w = d.w; a.m = d.m; a.n = d.n; a.k = d.k;
+    a.epi = d.epi; a.pair_off = d.epi == EPI_SILU_MUL ? d.n / 2 : 0;
+    a.y = d.y; a.y_hi = static_cast<_Float16*>(d.y_hi); a.y_lo = static_cast<_Float16*>(d.y_lo); a.ldy = d.ldy;
+    a.ksplit = d.ksplit; a.slab = d.slab;
+    a.lo8 = d.lo8; a.w8 = d.w8; a.w8_exp = d.w8_exp;
+    a.err = d.err;
+    *g = a;
+    Gemm2Args c = a;  // the plan functions fill n_tiles / ksplit: the launcher does that to its own copy
+    if (d.kernel == 2) return gemm2_plan(c, p);
+    LLMI_TRY(gemm3_plan(c, p));  // the argument checks before the stream-K decision
+    if (d.stream_k) {
+        int n_cu = 0;
+        if (gemm3_sk_decide(c, &n_cu) > 0) {
+            c.sk_grid = n_cu;
+            LLMI_TRY(gemm3_plan(c, p));
+        }
+    }
+    return LLMI_OK;
+}
+}  // namespace
+
+int llmi_debug_gemm(const llmi_debug_gemm_args* args, llmi_stream_t stream) {
+    Gemm2Args g;
+    GemmPlan p;
+    LLMI_TRY(debug_gemm_plan(args, &g, &p));  // nothing is allocated or launched on a refused call
+    if (args->kernel == 2) return gemm2_launch(g, STREAM(stream));
+    if (args->stream_k) (void)gemm3_sk_attach(g, STREAM(stream));  // as Engine::prefill_layer_gemm2
+    return gemm3_launch(g, STREAM(stream));
+}
+
+int llmi_debug_gemm_plan(const llmi_debug_gemm_args* args, int* bm, int* grid, int* sk_pmax) {
+    LLMI_REQUIRE(bm && grid && sk_pmax, "debug_gemm_plan: null outputs");
+    Gemm2Args g;
+    GemmPlan p;
+    LLMI_TRY(debug_gemm_plan(args, &g, &p));
+    *bm = p.bm; *grid = p.grid; *sk_pmax = p.sk_pmax;
+    return LLMI_OK;
+}
+
 int llmi_debug_rows_split(float* x, int ldx, int m, int k, const void* gamma, int g_dtype, float eps, void* hi,
                           void* lo, int ldh, const float* slab, int ksplit, int lo8, llmi_stream_t stream) {
     return rows_split_launch(x, ldx, m, k, gamma, g_dtype, eps, static_cast<_Float16*>(hi), static_cast<_Float16*>(lo),

@@ -372,9 +372,12 @@ int gemm2_bm(const Gemm2Args& a) {
     return ((a.m + 127) / 128) * nt >= 256 ? 128 : 64;
 }
 
-int gemm2_launch(Gemm2Args a, hipStream_t s) {
+int gemm2_plan(Gemm2Args& a, GemmPlan* p) {
+    LLMI_REQUIRE(p != nullptr, "gemm2 plan: null output");
     LLMI_REQUIRE(a.a[0] && a.w && a.m > 0, "gemm2: null operand or empty M");
     LLMI_REQUIRE(a.planes == 1 || (a.planes == 2 && a.a[1]), "gemm2: planes must be 1 or 2 (with a[1])");
+    LLMI_REQUIRE(a.epi == EPI_STORE || a.epi == EPI_ADD || a.epi == EPI_SILU_MUL || a.epi == EPI_SLAB,
+                 "gemm2: epilogue must be store, add, silu_mul or slab");
     LLMI_REQUIRE(gemm2_supported(a.n, a.k, a.epi), "gemm2: N a multiple of 128 (gate_up: 2 x 64), K of 64");
     LLMI_REQUIRE(a.epi == EPI_SILU_MUL ? (a.y || a.y_hi) : a.y != nullptr, "gemm2: null output");
     LLMI_REQUIRE(a.lda % 8 == 0 && (reinterpret_cast<uintptr_t>(a.a[0]) & 15) == 0 &&
@@ -393,10 +396,17 @@ int gemm2_launch(Gemm2Args a, hipStream_t s) {
     } else {
         a.ksplit = 1;
     }
-    const int bm = gemm2_bm(a);
-    const int grid = ((a.m + bm - 1) / bm) * a.n_tiles * a.ksplit;
-    if (bm == 128) return a.planes == 2 ? launch2<128, 2>(a, grid, s) : launch2<128, 1>(a, grid, s);
-    return a.planes == 2 ? launch2<64, 2>(a, grid, s) : launch2<64, 1>(a, grid, s);
+    p->bm = gemm2_bm(a);
+    p->tiles = p->grid = ((a.m + p->bm - 1) / p->bm) * a.n_tiles * a.ksplit;
+    p->sk_pmax = 0;
+    return LLMI_OK;
+}
+
+int gemm2_launch(Gemm2Args a, hipStream_t s) {
+    GemmPlan p;
+    LLMI_TRY(gemm2_plan(a, &p));
+    if (p.bm == 128) return a.planes == 2 ? launch2<128, 2>(a, p.grid, s) : launch2<128, 1>(a, p.grid, s);
+    return a.planes == 2 ? launch2<64, 2>(a, p.grid, s) : launch2<64, 1>(a, p.grid, s);
 }
 
 int rows_split_launch(float* x, int ldx, int m, int k, const void* gamma, int g_dtype, float eps, _Float16* hi,
@@ -638,19 +648,31 @@ int cu_count() {
 // stream-K for a gemm3 launch of these shapes when it keeps at most 3 partial slots per tile
 // (q/k/v and gate_up at 512 rows; o_proj / down, whose tiles would split 8 ways, keep the
 // split-K slices summed by their consumer). LLMI_SK=0 turns it off.
-bool sk_setup(Gemm2Args& g, hipStream_t s) {
+// the decision alone (no allocation): the stream-K plan when the launch takes it, pmax 0 when
+// not; *n_cu the workgroups it would run on (256 without a device, as the attention plan)
+Gemm3SkPlan sk_decide(const Gemm2Args& g, int* n_cu) {
     static const bool off = [] {
         const char* e = std::getenv("LLMI_SK");
         return e && std::string(e) == "0";
     }();
-    if (off) return false;
+    *n_cu = cu_count();
+    if (*n_cu <= 0) {
+        (void)hipGetLastError();
+        *n_cu = 256;
+    }
+    if (off) return Gemm3SkPlan();
     // one fp16 plane (the fp16-activation prefill): since the plain kernel's steady tiles run
     // paired (gemm3.hip, round 6) it is the faster form -- 512-row prefill 9.37-9.41 -> 9.17-9.18
     // ms on one box, while two planes and fp8 lo planes stay faster on stream-K (r06m)
-    if (g.planes == 1 && !g.lo8) return false;
-    const int n_cu = cu_count();
-    const Gemm3SkPlan p = gemm3_sk_plan(g.m, g.n, g.k, g.epi, g.planes, g.lo8, n_cu);
-    if (p.pmax < 1 || p.pmax > 3) return false;
+    if (g.planes == 1 && !g.lo8) return Gemm3SkPlan();
+    const Gemm3SkPlan p = gemm3_sk_plan(g.m, g.n, g.k, g.epi, g.planes, g.lo8, *n_cu);
+    if (p.pmax < 1 || p.pmax > 3) return Gemm3SkPlan();
+    return p;
+}
+bool sk_setup(Gemm2Args& g, hipStream_t s) {
+    int n_cu = 0;
+    const Gemm3SkPlan p = sk_decide(g, &n_cu);
+    if (p.pmax < 1) return false;
     if (sk_workspace(s, p.slab_bytes, p.flag_bytes, &g.sk_slab, &g.sk_flags, &g.sk_ctl) != LLMI_OK) return false;
     // a partial that never arrives sets bit 16 somewhere the caller can read (stream_errors)
     if (!g.err && stream_error_word(s, &g.err) != LLMI_OK) return false;
@@ -658,6 +680,13 @@ bool sk_setup(Gemm2Args& g, hipStream_t s) {
     return true;
 }
 }  // namespace
+
+int gemm3_sk_decide(const Gemm2Args& g, int* n_cu) {
+    int n = 0;
+    const int pmax = sk_decide(g, &n).pmax;
+    if (n_cu) *n_cu = n;
+    return pmax;
+}
 
 bool gemm3_sk_attach(Gemm2Args& g, hipStream_t s) { return sk_setup(g, s); }
 

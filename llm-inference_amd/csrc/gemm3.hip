@@ -125,6 +125,12 @@ __device__ __forceinline__ void bar() {
 
 __device__ __forceinline__ float silu3(float v) { return v / (1.0f + expf(-v)); }
 
+// one byte of lo8_pack4 (common.h): the same scale, clamp and conversion
+__device__ __forceinline__ unsigned char lo8_byte(float l) {
+    const float c = fminf(fmaxf(l * (float)(1 << kLo8Exp), -448.f), 448.f);
+    return (unsigned char)__builtin_amdgcn_cvt_pk_fp8_f32(c, c, 0, false);
+}
+
 // One tile's K loop into acc: nhi 64-deep fp16 K tiles of the hi plane from tile hi0, then
 // nlo tiles of the lo plane from tile lo0 (fp16 plane: 64-deep tiles; lo8: 128-deep fp8
 // tiles; both 128 B per LDS row). nhi + nlo >= 2: the prologue's counted wait covers the
@@ -385,36 +391,48 @@ __device__ __forceinline__ void g3_epilogue(const Gemm2Args& a, char* lds, f4v (
         // (measured store-issue-bound: 7-10 us of a 110 us gate_up). Rows padded to 272 B:
         // the accumulator rows 4 apart land 16 banks apart.
         char* img = lds;
+        // F8: the lo image holds e4m3 bytes (128 B of each 272-B row) of the exact fp32 remainder,
+        // as rows_split_kernel writes them -- converted from the fp16 lo instead, the byte was
+        // rounded twice and came out one e4m3 step off on ~0.5 % of the elements
+        auto fill = [&](auto f8) {
 #pragma unroll
-        for (int qa = 0; qa < 2; ++qa)
+            for (int qa = 0; qa < 2; ++qa)
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+                for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int e = 0; e < 4; ++e)
+                    for (int e = 0; e < 4; ++e)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const int row = qa * 128 + wr * 64 + 16 * i + 4 * fq + e, col = wc * 32 + 16 * j + fr;
-                        const float v = silu3(acc[qa][0][i][j][e]) * acc[qa][1][i][j][e];
-                        const _Float16 hi = (_Float16)v;
-                        *reinterpret_cast<_Float16*>(img + row * kEpiRowB + col * 2) = hi;
-                        if (a.y_lo)
-                            *reinterpret_cast<_Float16*>(img + (kTile + row) * kEpiRowB + col * 2) =
-                                (_Float16)(v - (float)hi);
-                    }
+                        for (int j = 0; j < 2; ++j) {
+                            const int row = qa * 128 + wr * 64 + 16 * i + 4 * fq + e, col = wc * 32 + 16 * j + fr;
+                            float v = silu3(acc[qa][0][i][j][e]) * acc[qa][1][i][j][e];
+                            // the fp32 product stays a value of its own: folded into the conversion
+                            // (v_fma_mixlo_f16 s, u, +0) an exact -0 product -- silu(g) is -0 once
+                            // expf(-g) overflows -- came out as +0, not fp16(v)
+                            asm("" : "+v"(v));
+                            const _Float16 hi = (_Float16)v;
+                            *reinterpret_cast<_Float16*>(img + row * kEpiRowB + col * 2) = hi;
+                            if constexpr (decltype(f8)::value)
+                                *reinterpret_cast<unsigned char*>(img + (kTile + row) * kEpiRowB + col) =
+                                    lo8_byte(v - (float)hi);
+                            else if (a.y_lo)
+                                *reinterpret_cast<_Float16*>(img + (kTile + row) * kEpiRowB + col * 2) =
+                                    (_Float16)(v - (float)hi);
+                        }
+        };
+        if (lo8 && a.y_lo) fill(std::true_type{});
+        else fill(std::false_type{});
         __syncthreads();
         const int planes = a.y_lo ? 2 : 1;
         for (int c = t; c < planes * kTile * 16; c += kT) {
             const int pl = c / (kTile * 16), row = (c >> 4) & (kTile - 1), ch = c & 15;
             const int m = m0 + row;
             if (m >= a.m) continue;
-            const h8v v = *reinterpret_cast<const h8v*>(img + (pl * kTile + row) * kEpiRowB + ch * 16);
             if (pl && lo8) {  // e4m3 bytes [m, ldy] of the lo plane
-                uint2 q;
-                q.x = lo8_pack4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
-                q.y = lo8_pack4((float)v[4], (float)v[5], (float)v[6], (float)v[7]);
+                const uint2 q = *reinterpret_cast<const uint2*>(img + (kTile + row) * kEpiRowB + ch * 8);
                 *reinterpret_cast<uint2*>(reinterpret_cast<char*>(a.y_lo + (size_t)m * a.ldy) + ct * 128 + ch * 8) = q;
                 continue;
             }
+            const h8v v = *reinterpret_cast<const h8v*>(img + (pl * kTile + row) * kEpiRowB + ch * 16);
             _Float16* dst = (pl ? a.y_lo : a.y_hi) + (size_t)m * a.ldy + ct * 128 + ch * 8;
             *reinterpret_cast<h8v*>(dst) = v;
         }
@@ -901,9 +919,12 @@ bool gemm3_supported(int n, int k, int epi, int ksplit) {
     return n > 0 && k > 0 && s >= 1 && ncols % tile == 0 && k % kK == 0 && k / kK / s >= 2;  // slices may be uneven
 }
 
-int gemm3_launch(Gemm2Args a, hipStream_t s) {
+int gemm3_plan(Gemm2Args& a, GemmPlan* p) {
+    LLMI_REQUIRE(p != nullptr, "gemm3 plan: null output");
     LLMI_REQUIRE(a.a[0] && a.w && a.m > 0, "gemm3: null operand or empty M");
     LLMI_REQUIRE(a.planes == 1 || (a.planes == 2 && a.a[1]), "gemm3: planes must be 1 or 2 (with a[1])");
+    LLMI_REQUIRE(a.epi == EPI_STORE || a.epi == EPI_ADD || a.epi == EPI_SILU_MUL || a.epi == EPI_SLAB,
+                 "gemm3: epilogue must be store, add, silu_mul or slab");
     if (a.epi != EPI_SLAB) a.ksplit = 1;
     LLMI_REQUIRE(gemm3_supported(a.n, a.k, a.epi, a.ksplit),
                  "gemm3: N a multiple of 256 (gate_up: 2 x 128), K a multiple of 64, >= 2 K tiles of 64 per slice");
@@ -928,7 +949,23 @@ int gemm3_launch(Gemm2Args a, hipStream_t s) {
                  "and (gate_up) both output planes");
     const int ncols = (a.epi == EPI_SILU_MUL) ? a.n / 2 : a.n;
     a.n_tiles = ncols / ((a.epi == EPI_SILU_MUL) ? 128 : kTile);
-    const int grid = ((a.m + kTile - 1) / kTile) * a.n_tiles * a.ksplit;
+    p->bm = kTile;
+    p->tiles = p->grid = ((a.m + kTile - 1) / kTile) * a.n_tiles * a.ksplit;
+    p->sk_pmax = 0;
+    // stream-K (gemm3_sk_attach set sk_grid): its workgroups instead of one per tile
+    if (a.sk_grid > 0 && (a.epi == EPI_STORE || a.epi == EPI_SILU_MUL)) {
+        const Gemm3SkPlan sk = gemm3_sk_plan(a.m, a.n, a.k, a.epi, a.planes, a.lo8, a.sk_grid);
+        LLMI_REQUIRE(sk.pmax > 0, "gemm3: stream-K requested for a shape it does not cover (see gemm3_sk_plan)");
+        p->sk_pmax = sk.pmax;
+        p->grid = a.sk_grid;
+    }
+    return LLMI_OK;
+}
+
+int gemm3_launch(Gemm2Args a, hipStream_t s) {
+    GemmPlan plan;
+    LLMI_TRY(gemm3_plan(a, &plan));
+    const int grid = plan.tiles;
     if (a.epi == EPI_SILU_MUL && a.planes == 2 && a.bal_slab && a.bal_flags) {
         // every CU busy: lo workers beside the tile owners, when the split is even enough
         // (a tile touched by at most two workers) and the slots are large enough
@@ -958,15 +995,13 @@ int gemm3_launch(Gemm2Args a, hipStream_t s) {
             return LLMI_OK;
         }
     }
-    if (a.sk_slab && a.sk_flags && a.sk_grid > 0 && (a.epi == EPI_STORE || a.epi == EPI_SILU_MUL)) {
-        const Gemm3SkPlan p = gemm3_sk_plan(a.m, a.n, a.k, a.epi, a.planes, a.lo8, a.sk_grid);
-        LLMI_REQUIRE(p.pmax > 0, "gemm3: stream-K requested for a shape it does not cover (see gemm3_sk_plan)");
-        LLMI_REQUIRE(a.sk_ctl && a.sk_ctl + kSkCtlWords == a.sk_flags,
-                     "gemm3: stream-K needs its control words just before the flags (sk_workspace)");
+    if (plan.sk_pmax > 0) {
+        LLMI_REQUIRE(a.sk_slab && a.sk_flags && a.sk_ctl && a.sk_ctl + kSkCtlWords == a.sk_flags,
+                     "gemm3: stream-K needs its slots and its control words just before the flags (sk_workspace)");
         int left = g_sk_debug_left.load();
         while (left > 0 && !g_sk_debug_left.compare_exchange_weak(left, left - 1)) {
         }
-        a.sk_pmax = p.pmax | ((left > 0 ? g_sk_debug_mode.load() : 0) << 8);  // + the fault-injection mode
+        a.sk_pmax = plan.sk_pmax | ((left > 0 ? g_sk_debug_mode.load() : 0) << 8);  // + the fault-injection mode
         if (a.epi == EPI_STORE) return launch_sk<EPI_STORE>(a, s);
         return launch_sk<EPI_SILU_MUL>(a, s);
     }

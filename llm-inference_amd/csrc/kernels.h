@@ -221,6 +221,19 @@ Gemm3SkPlan gemm3_sk_plan(int m, int n, int k, int epi, int planes, int lo8, int
 // attach the stream-K workspace (per device and stream, gemm2.hip) to a gemm3 launch of g's
 // shape when the plan keeps <= 3 slots a tile; false: launch as before (LLMI_SK=0: never)
 bool gemm3_sk_attach(Gemm2Args& g, hipStream_t s);
+// gemm3_sk_attach's decision alone, nothing allocated (attach takes it from the same function):
+// the slots per tile, 0 when it would decline; *n_cu (optional) the workgroups it would run on
+// (the CU count; 256 without a device)
+int gemm3_sk_decide(const Gemm2Args& g, int* n_cu);
+// what gemm2_launch / gemm3_launch would run for a, nothing launched (the launchers call them
+// too): every argument check, n_tiles / ksplit set in a, then the row tile (gemm2: 64 or 128;
+// gemm3: 256), the output tiles x K slices, the workgroup count (stream-K: sk_grid) and the
+// stream-K slots per tile (0: the plain kernel)
+struct GemmPlan {
+    int bm = 0, tiles = 0, grid = 0, sk_pmax = 0;
+};
+int gemm2_plan(Gemm2Args& a, GemmPlan* p);
+int gemm3_plan(Gemm2Args& a, GemmPlan* p);
 // reads and clears the sticky error bits that launches on s (this device) recorded when
 // their caller passed no error word (16: a stream-K partial never arrived); syncs s
 int stream_errors(hipStream_t s, int* flags);

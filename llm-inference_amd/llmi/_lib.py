@@ -82,7 +82,16 @@ class DebugPrefillAttnArgs(C.Structure):
                 ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
 
 
-_P, _I, _U64, _U32, _F, _SZ = C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_size_t
+class DebugGemmArgs(C.Structure):
+    """llmi_debug_gemm_args (include/llmi.h), field for field."""
+    _fields_ = [("kernel", C.c_int), ("a_hi", C.c_void_p), ("a_lo", C.c_void_p), ("planes", C.c_int),
+                ("lda", C.c_int), ("w", C.c_void_p), ("m", C.c_int), ("n", C.c_int), ("k", C.c_int),
+                ("epi", C.c_int), ("y", C.c_void_p), ("y_hi", C.c_void_p), ("y_lo", C.c_void_p),
+                ("ldy", C.c_int), ("ksplit", C.c_int), ("slab", C.c_void_p), ("lo8", C.c_int),
+                ("w8", C.c_void_p), ("w8_exp", C.c_int), ("stream_k", C.c_int), ("err", C.c_void_p)]
+
+
+_P, _I, _U64, _U32, _F, _SZ =C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_size_t
 _SIGS = {
     "llmi_last_error": (C.c_char_p, []),
     "llmi_version": (C.c_char_p, []),
@@ -130,6 +139,8 @@ _SIGS = {
     "llmi_debug_prefill_attn": (_I, [C.POINTER(DebugPrefillAttnArgs), _P]),
     "llmi_debug_prefill_attn_plan": (_I, [C.POINTER(DebugPrefillAttnArgs), C.POINTER(_I), C.POINTER(_I),
                                           C.POINTER(_I), C.POINTER(_I)]),
+    "llmi_debug_gemm": (_I, [C.POINTER(DebugGemmArgs), _P]),
+    "llmi_debug_gemm_plan": (_I, [C.POINTER(DebugGemmArgs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "llmi_debug_rows_split": (_I, [_P, _I, _I, _I, _P, _I, _F, _P, _P, _I, _P, _I, _I, _P]),
     "llmi_debug_w8_prepare": (_I, [_P, _I, _I, _P, C.POINTER(_I), _P]),
     "llmi_hbm_read_bench": (_I, [_SZ, _I, _P, _P, _P]),

@@ -151,6 +151,103 @@ def test_debug_prefill_attn_plan_walks_the_ladder():
     assert _pf_plan(out=0, out_hi=0x1000, **ok) == (1, 1, 8, 0)
 
 
+EPI_STORE, EPI_ADD, EPI_SILU, EPI_SLAB = 0, 1, 2, 5
+# (kernel, m, n, k, epi, ksplit) of tests/test_gpu_prefill_gemm.py's sections A and C
+GEMM_SHAPES = \
+    [(2, m, n, k, EPI_STORE, 0) for m, n, k in ((1, 128, 64), (63, 128, 128), (64, 256, 192), (65, 128, 256),
+                                                (129, 384, 320), (300, 128, 576), (257, 11008, 192),
+                                                (300, 11008, 64), (130, 10240, 64))] + \
+    [(2, 77, 256, 192, EPI_ADD, 0), (2, 130, 128, 64, EPI_ADD, 0)] + \
+    [(2, m, n, k, EPI_SLAB, s) for m, n, k, s in ((16, 128, 64, 1), (100, 256, 512, 2), (130, 128, 192, 3),
+                                                  (64, 128, 512, 8))] + \
+    [(2, m, 2 * i, k, EPI_SILU, 0) for m, i, k in ((65, 64, 128), (130, 192, 64), (257, 5504, 64))] + \
+    [(3, m, n, k, EPI_STORE, 0) for m, n, k in ((1, 256, 128), (255, 256, 192), (256, 512, 256), (257, 256, 320),
+                                                (257, 256, 384), (300, 512, 448), (513, 256, 128),
+                                                (513, 256, 192), (300, 12288, 512))] + \
+    [(3, 300, 256, 128, EPI_ADD, 0), (3, 257, 512, 192, EPI_ADD, 0)] + \
+    [(3, 300, n, k, EPI_SLAB, s) for n, k, s in ((256, 320, 2), (512, 832, 4), (256, 384, 2), (512, 1152, 8))] + \
+    [(3, m, 2 * i, k, EPI_SILU, 0) for m, i, k in ((1, 128, 128), (257, 256, 192), (300, 384, 256))]
+# section D: (epi, lo8, m, n, k, sk_pmax) for 256 workgroups
+GEMM_SK = [(EPI_SILU, 0, 300, 2 * 4096, 512, 3), (EPI_SILU, 0, 300, 2 * 8192, 256, 1),
+           (EPI_SILU, 1, 512, 2 * 6144, 512, 2), (EPI_STORE, 0, 300, 8192, 512, 3), (EPI_STORE, 1, 300, 12288, 512, 2)]
+
+
+def _gemm_plan(**kw):
+    F = 0x1000  # never dereferenced
+    a = _lib.DebugGemmArgs()
+    base = dict(kernel=2, a_hi=F, a_lo=F, planes=2, w=F, y=F, m=64, n=256, k=128)
+    kw = dict(base, **kw)
+    kw.setdefault("lda", kw["k"])
+    kw.setdefault("ldy", kw["n"] // 2 if kw.get("epi") == EPI_SILU else kw["n"])
+    for key, v in kw.items():
+        setattr(a, key, v)
+    o = [C.c_int() for _ in range(3)]
+    call("llmi_debug_gemm_plan", C.byref(a), *[C.byref(x) for x in o])
+    return tuple(x.value for x in o)
+
+
+def _gemm_model(kernel, m, n, k, epi, ks):
+    """The launchers' rule restated: gemm2 tiles 128 columns (gate_up: 64 gate columns), rows by
+    128 iff split-K or ceil(m / 128) x column tiles >= 256, else by 64; gemm3 tiles 256 x 256
+    (gate_up: 128 gate columns); one workgroup per tile and K slice."""
+    s = ks if epi == EPI_SLAB else 1
+    if kernel == 2:
+        nt = (n // 2) // 64 if epi == EPI_SILU else n // 128
+        bm = 128 if epi == EPI_SLAB or -(-m // 128) * nt >= 256 else 64
+    else:
+        nt = (n // 2) // 128 if epi == EPI_SILU else n // 256
+        bm = 256
+    return bm, -(-m // bm) * nt * s, 0
+
+
+def test_debug_gemm_plan_reports_the_launchers_choices():
+    """llmi_debug_gemm_plan launches and allocates nothing; without a GPU the CU count falls back
+    to 256. bm and grid for the shapes of the GPU file against the rule restated above, one and
+    two planes; the stream-K slots of the GPU file's section D (and the forms stream-K declines);
+    then every argument check of the two launchers and of the hook."""
+    F = 0x1000
+    for kernel, m, n, k, epi, ks in GEMM_SHAPES:
+        for planes in (1, 2):
+            kw = dict(kernel=kernel, m=m, n=n, k=k, epi=epi, ksplit=ks, planes=planes, slab=F if epi == EPI_SLAB else 0)
+            assert _gemm_plan(**kw) == _gemm_model(kernel, m, n, k, epi, ks), kw
+    assert _gemm_plan(kernel=2, m=257, n=11008, k=192)[0] == 128 and _gemm_plan(kernel=2, m=300, n=11008, k=64)[0] == 128
+    assert _gemm_plan(kernel=2, m=257, n=2 * 5504, k=64, epi=EPI_SILU)[0] == 128
+    assert _gemm_plan(kernel=2, m=256, n=11008, k=192)[0] == 64            # 2 x 86 tiles < 256
+    assert _gemm_plan(kernel=2, m=130, n=10240, k=64) == (64, 3 * 80, 0)    # 2 x 80 tiles >= 160: llmi_linear's ks = 1
+    lo8 = dict(lo8=1, w8=F, w8_exp=-12)
+    for epi, l8, m, n, k, pmax in GEMM_SK:
+        kw = dict(kernel=3, m=m, n=n, k=k, epi=epi, y_hi=F, y_lo=F, **(lo8 if l8 else {}))
+        assert _gemm_plan(stream_k=1, **kw) == (256, 256, pmax), kw          # every CU one workgroup
+        assert _gemm_plan(stream_k=0, **kw) == _gemm_model(3, m, n, k, epi, 0), kw
+        if not l8:                                                           # one plane: the plain kernel
+            assert _gemm_plan(stream_k=1, **dict(kw, planes=1)) == _gemm_model(3, m, n, k, epi, 0), kw
+    # declined: the tiles fill the CUs; fewer than two K-tile pairs a workgroup; split-K and add have no stream-K form
+    assert _gemm_plan(kernel=3, stream_k=1, m=2048, n=8192, k=512) == (256, 256, 0)
+    assert _gemm_plan(kernel=3, stream_k=1, m=300, n=512, k=4096) == (256, 4, 0)
+    assert _gemm_plan(kernel=3, stream_k=1, m=300, n=8192, k=512, epi=EPI_ADD) == (256, 64, 0)
+    assert _gemm_plan(kernel=3, stream_k=1, m=300, n=8192, k=512, epi=EPI_SLAB, ksplit=2, slab=F) == (256, 128, 0)
+    g3 = dict(kernel=3, m=300, n=256, k=256)
+    for bad in (dict(a_hi=0), dict(w=0), dict(m=0), dict(planes=0), dict(planes=3), dict(a_lo=0), dict(n=192),
+                dict(k=96), dict(lda=132), dict(a_hi=F + 8), dict(a_lo=F + 8), dict(w=F + 8), dict(y=0),
+                dict(epi=EPI_SILU, y=0), dict(epi=3), dict(epi=EPI_SLAB, ksplit=2), dict(epi=EPI_SLAB, ksplit=0, slab=F)):
+        for base in (dict(), g3):
+            with pytest.raises(_lib.LlmiError):
+                _gemm_plan(**dict(base, **bad))
+    for bad in (dict(epi=EPI_SLAB, slab=F, ksplit=3), dict(kernel=4), dict(kernel=0), dict(stream_k=1), dict(stream_k=2, kernel=3),
+                dict(kernel=2, **lo8), dict(epi=EPI_SILU, n=192)):
+        with pytest.raises(_lib.LlmiError):
+            _gemm_plan(**bad)                                                # gemm2: k 128 in 3 slices; the hook's own checks
+    for bad in (dict(k=64), dict(epi=EPI_SLAB, slab=F, ksplit=3), dict(planes=1, **lo8), dict(lo8=1, w8=0),
+                dict(lo8=1, w8=F + 8), dict(k=192, **lo8), dict(epi=EPI_SLAB, slab=F, ksplit=3, k=256, **lo8),
+                dict(epi=EPI_SILU, y_hi=F, y_lo=0, **lo8), dict(epi=EPI_SILU, y=F, **lo8),
+                dict(epi=EPI_SILU, y=0, y_hi=F, ldy=132), dict(epi=EPI_SILU, y=0, y_hi=F + 8), dict(n=384)):
+        with pytest.raises(_lib.LlmiError):
+            _gemm_plan(**dict(g3, **bad))
+    assert _gemm_plan(epi=EPI_SILU, y=0, y_hi=F) == (64, 2, 0)
+    assert _gemm_plan(**dict(g3, epi=EPI_SLAB, slab=F, ksplit=2, y=0)) == (256, 4, 0)   # gemm3's slab form needs no y
+    assert _gemm_plan(**dict(g3, epi=EPI_SLAB, slab=F, ksplit=2, **lo8)) == (256, 4, 0)  # one fp8 tile a slice
+
+
 def test_debug_gemv_plan_reports_the_launchers_choices():
     """llmi_debug_gemv_plan launches nothing, so its ladder is checked without a GPU: the
     x-staging width at each threshold (k / 4 float4s against 4, 5, 11, 14 x 256), the unroll
