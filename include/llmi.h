@@ -363,6 +363,35 @@ typedef struct llmi_debug_gemm_args {
 int llmi_debug_gemm(const llmi_debug_gemm_args* args, llmi_stream_t stream);
 int llmi_debug_gemm_plan(const llmi_debug_gemm_args* args, int* bm, int* grid, int* sk_pmax);
 
+/* llmi_debug_gemm1: one launch of the first-generation prefill GEMM (gemm.hip, the GEMM of the
+ * int8 engines), its argument block (GemmArgs) filled field for field and handed to the
+ * production launcher (test-only: no engine or operator path calls it). a: fp32 [m, lda],
+ * split into fp16 planes while it is staged (split 2: hi + lo; 1: hi alone); gamma (g_dtype
+ * LLMI_F16 / LLMI_F32, [k]; NULL: none): the RMSNorm of each a row folded in, with eps.
+ * w: [n, k] of w_dtype LLMI_F16, or LLMI_I8 with scales, one fp16 per row. epi: 0 store (with
+ * or without gamma), 1 add (y += .., no gamma), 2 gate_up (with gamma; w = [gate; up] rows,
+ * n = 2 x inter, the pair offset is set to n / 2: y [m, ldy] = silu(gate) * up). w_kblock is
+ * not exposed and stays 0. Nothing is launched on a refused call. The caller owns every buffer.
+ * llmi_debug_gemm1_plan launches and allocates nothing: it runs the launcher's argument checks
+ * and reports the row tile (bm: 64 or 128) and the workgroup count. */
+typedef struct llmi_debug_gemm1_args {
+    const float* a;
+    int lda;
+    const void* gamma;
+    int g_dtype;
+    float eps;
+    const void* w;
+    int w_dtype;
+    const void* scales;
+    int m, n, k;
+    int split;
+    int epi;
+    float* y;
+    int ldy;
+} llmi_debug_gemm1_args;
+int llmi_debug_gemm1(const llmi_debug_gemm1_args* args, llmi_stream_t stream);
+int llmi_debug_gemm1_plan(const llmi_debug_gemm1_args* args, int* bm, int* grid);
+
 /* llmi_debug_rows_split: the prefill GEMMs' activation producer. Rows of x [m, ldx] (k used):
  * with slab [ksplit][m][k] (ldx == k) x += slice 0 + slice 1 + ... in that order, written
  * back; then optional RMSNorm (gamma [k] of g_dtype f16 / f32; NULL: none); then fp16 planes

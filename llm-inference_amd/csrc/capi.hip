@@ -340,6 +340,40 @@ int llmi_debug_gemm_plan(const llmi_debug_gemm_args* args, int* bm, int* grid, i
     return LLMI_OK;
 }
 
+namespace {
+// gemm.hip's argument block from the hook's, field for field (w_kblock stays 0)
+int debug_gemm1_args(const llmi_debug_gemm1_args* args, GemmArgs* g) {
+    LLMI_REQUIRE(args != nullptr, "debug_gemm1: null arguments");
+    const llmi_debug_gemm1_args& d = *args;
+    GemmArgs a;
+    a.a = d.a; a.lda = d.lda;
+    a.gamma = d.gamma; a.g_dtype = d.g_dtype; a.eps = d.eps;
+    a.w = d.w; a.w_dtype = d.w_dtype; a.scales = reinterpret_cast<const __half*>(d.scales);
+    a.m = d.m; a.n = d.n; a.k = d.k;
+    a.split = d.split;
+    a.epi = d.epi; a.pair_off = d.epi == EPI_SILU_MUL ? d.n / 2 : 0;
+    a.y = d.y; a.ldy = d.ldy;
+    *g = a;
+    return LLMI_OK;
+}
+}  // namespace
+
+int llmi_debug_gemm1(const llmi_debug_gemm1_args* args, llmi_stream_t stream) {
+    GemmArgs g;
+    LLMI_TRY(debug_gemm1_args(args, &g));
+    return gemm_launch(g, STREAM(stream));  // gemm_plan first: nothing is launched on a refused call
+}
+
+int llmi_debug_gemm1_plan(const llmi_debug_gemm1_args* args, int* bm, int* grid) {
+    LLMI_REQUIRE(bm && grid, "debug_gemm1_plan: null outputs");
+    GemmArgs g;
+    GemmPlan p;
+    LLMI_TRY(debug_gemm1_args(args, &g));
+    LLMI_TRY(gemm_plan(g, &p));
+    *bm = p.bm; *grid = p.grid;
+    return LLMI_OK;
+}
+
 int llmi_debug_rows_split(float* x, int ldx, int m, int k, const void* gamma, int g_dtype, float eps, void* hi,
                           void* lo, int ldh, const float* slab, int ksplit, int lo8, llmi_stream_t stream) {
     return rows_split_launch(x, ldx, m, k, gamma, g_dtype, eps, static_cast<_Float16*>(hi), static_cast<_Float16*>(lo),

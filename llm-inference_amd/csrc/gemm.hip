@@ -7,8 +7,16 @@
 // f16 MFMA exactly. The fp32 activations are split while they are staged:
 // a = hi + lo with hi = fp16(a), lo = fp16(a - hi), and both halves are
 // multiplied against the same W fragment (SPLIT = 2), accumulating in fp32.
-// That keeps the product fp32-faithful (|a - hi - lo| <= 2^-22 |a|) for twice
-// the MFMA work; SPLIT = 1 (plain fp16 activations) measured 2.3e-3 logits
+// That keeps the product fp32-faithful for twice the MFMA work, over a range:
+// |a - hi - lo| <= max(2^-22 |a|, 2^-25), i.e. 2^-22 |a| for |a| >= 2^-3
+// (lo <= 2^-11 |a| is rounded to fp16's grid, whose spacing stops at 2^-24).
+// lo is not scaled, so below that it sinks into the subnormals (which the MFMA
+// does multiply: the kernel follows a numpy model of the planes) and the
+// relative error grows as 1 / |a|, up to hi alone's. Measured at (64, 128, 1024), max row rel-L2 against
+// float64 x W^T: 3.7e-7 for x ~ N(0, 1) x 2^0 .. 2^12, 4.0e-7 at 2^-3, 7.1e-7
+// at 2^-5, 2.7e-6 at 2^-7, 1.0e-5 at 2^-9 (hi alone: 2.6e-4); the table is in
+// DESIGN.md ("First-generation GEMM, one form at a time"). SPLIT = 1 (plain
+// fp16 activations) measured 2.3e-3 logits
 // rel-L2 over 32 layers vs the fp32 reference -- over the 1e-3 bar -- so it is
 // kept only as the throughput variant.
 //
@@ -248,18 +256,17 @@ __global__ __launch_bounds__(kThreads) void gemm_kernel(GemmArgs a) {
     }
 }
 
+// the epilogue / norm combinations that exist (gemm_plan refuses every other one before this)
 template <int BM, int SPLIT, int WT>
 int dispatch_epi(const GemmArgs& a, dim3 grid, hipStream_t s) {
     if (a.epi == EPI_STORE && a.gamma)
         hipLaunchKernelGGL((gemm_kernel<BM, SPLIT, WT, EPI_STORE, true>), grid, dim3(kThreads), 0, s, a);
     else if (a.epi == EPI_STORE)
         hipLaunchKernelGGL((gemm_kernel<BM, SPLIT, WT, EPI_STORE, false>), grid, dim3(kThreads), 0, s, a);
-    else if (a.epi == EPI_ADD && !a.gamma)
+    else if (a.epi == EPI_ADD)
         hipLaunchKernelGGL((gemm_kernel<BM, SPLIT, WT, EPI_ADD, false>), grid, dim3(kThreads), 0, s, a);
-    else if (a.epi == EPI_SILU_MUL && a.gamma)
-        hipLaunchKernelGGL((gemm_kernel<BM, SPLIT, WT, EPI_SILU_MUL, true>), grid, dim3(kThreads), 0, s, a);
     else
-        LLMI_REQUIRE(false, "gemm: unsupported epilogue/norm combination");
+        hipLaunchKernelGGL((gemm_kernel<BM, SPLIT, WT, EPI_SILU_MUL, true>), grid, dim3(kThreads), 0, s, a);
     LLMI_HIP(hipGetLastError());
     return LLMI_OK;
 }
@@ -289,23 +296,41 @@ int gemm_bm(const GemmArgs& a) {
     return ((a.m + 127) / 128) * nt >= 256 ? 128 : 64;
 }
 
-int gemm_launch(GemmArgs a, hipStream_t s) {
+int gemm_plan(GemmArgs& a, GemmPlan* p) {
+    LLMI_REQUIRE(p != nullptr, "gemm plan: null output");
     LLMI_REQUIRE(a.a && a.w && a.y && a.m > 0, "gemm: null operand or empty M");
+    LLMI_REQUIRE(a.epi == EPI_STORE || a.epi == EPI_ADD || a.epi == EPI_SILU_MUL,
+                 "gemm: epilogue must be store, add or silu_mul");
     LLMI_REQUIRE(gemm_supported(a.w_dtype, a.n, a.k, a.epi),
                  "gemm: needs f16/i8 weights, N a multiple of 128 (gate_up: 2 x 64) and K of 64");
     LLMI_REQUIRE(a.w_dtype != LLMI_I8 || a.scales, "gemm: int8 weights need per-row scales");
-    LLMI_REQUIRE(a.lda % 4 == 0 && (reinterpret_cast<uintptr_t>(a.a) & 15) == 0, "gemm: A rows must be 16-B aligned");
+    LLMI_REQUIRE(a.lda >= a.k && a.lda % 4 == 0 && (reinterpret_cast<uintptr_t>(a.a) & 15) == 0,
+                 "gemm: A rows must hold K elements and be 16-B aligned");
     LLMI_REQUIRE((reinterpret_cast<uintptr_t>(a.w) & 15) == 0, "gemm: W must be 16-B aligned");
     LLMI_REQUIRE(a.split == 1 || a.split == 2, "gemm: split must be 1 or 2");
     LLMI_REQUIRE(a.w_kblock == 0 || (a.w_kblock % kBK == 0 && a.k % a.w_kblock == 0 && a.epi != EPI_SILU_MUL),
                  "gemm: w_kblock must be a multiple of 64 dividing K (not with the gate_up pairing)");
     LLMI_REQUIRE(a.epi != EPI_SILU_MUL || a.pair_off == a.n / 2, "gemm: gate_up pair offset must be N / 2");
+    // store with or without the norm, add without, gate_up with
+    LLMI_REQUIRE(a.epi == EPI_STORE || (a.epi == EPI_ADD && !a.gamma) || (a.epi == EPI_SILU_MUL && a.gamma),
+                 "gemm: unsupported epilogue/norm combination");
+    LLMI_REQUIRE(!a.gamma || ((a.g_dtype == LLMI_F32 && (reinterpret_cast<uintptr_t>(a.gamma) & 15) == 0) ||
+                              (a.g_dtype == LLMI_F16 && (reinterpret_cast<uintptr_t>(a.gamma) & 7) == 0)),
+                 "gemm: gamma must be f32 (16-B aligned) or f16 (8-B aligned)");
     const int ncols = (a.epi == EPI_SILU_MUL) ? a.n / 2 : a.n;
+    LLMI_REQUIRE(a.ldy >= ncols, "gemm: ldy must hold the output columns (N; gate_up: N / 2)");
     a.n_tiles = ncols / ((a.epi == EPI_SILU_MUL) ? kBN / 2 : kBN);
-    const int bm = gemm_bm(a);
-    const int mt = (a.m + bm - 1) / bm;
-    const dim3 grid(mt * a.n_tiles);
-    return bm == 128 ? dispatch_bm<128>(a, grid, s) : dispatch_bm<64>(a, grid, s);
+    p->bm = gemm_bm(a);
+    p->tiles = p->grid = ((a.m + p->bm - 1) / p->bm) * a.n_tiles;
+    p->sk_pmax = 0;
+    return LLMI_OK;
+}
+
+int gemm_launch(GemmArgs a, hipStream_t s) {
+    GemmPlan p;
+    LLMI_TRY(gemm_plan(a, &p));
+    const dim3 grid(p.grid);
+    return p.bm == 128 ? dispatch_bm<128>(a, grid, s) : dispatch_bm<64>(a, grid, s);
 }
 
 }  // namespace llmi

@@ -151,7 +151,7 @@ struct GemmArgs {
     int pair_off = 0;              // EPI_SILU_MUL: row offset of `up` in W (= n / 2)
     float* y = nullptr;            // [m, ldy]
     int ldy = 0;
-    int n_tiles = 0;               // set by gemm_launch
+    int n_tiles = 0;               // set by gemm_plan (gemm_launch calls it)
 };
 bool gemm_supported(int w_dtype, int n, int k, int epi);
 int gemm_bm(const GemmArgs& a);
@@ -232,6 +232,7 @@ int gemm3_sk_decide(const Gemm2Args& g, int* n_cu);
 struct GemmPlan {
     int bm = 0, tiles = 0, grid = 0, sk_pmax = 0;
 };
+int gemm_plan(GemmArgs& a, GemmPlan* p);  // gemm.hip: bm 64 or 128, one workgroup a tile, no stream-K
 int gemm2_plan(Gemm2Args& a, GemmPlan* p);
 int gemm3_plan(Gemm2Args& a, GemmPlan* p);
 // reads and clears the sticky error bits that launches on s (this device) recorded when

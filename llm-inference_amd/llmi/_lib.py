@@ -91,6 +91,14 @@ class DebugGemmArgs(C.Structure):
                 ("w8", C.c_void_p), ("w8_exp", C.c_int), ("stream_k", C.c_int), ("err", C.c_void_p)]
 
 
+class DebugGemm1Args(C.Structure):
+    """llmi_debug_gemm1_args (include/llmi.h), field for field."""
+    _fields_ = [("a", C.c_void_p), ("lda", C.c_int), ("gamma", C.c_void_p), ("g_dtype", C.c_int),
+                ("eps", C.c_float), ("w", C.c_void_p), ("w_dtype", C.c_int), ("scales", C.c_void_p),
+                ("m", C.c_int), ("n", C.c_int), ("k", C.c_int), ("split", C.c_int), ("epi", C.c_int),
+                ("y", C.c_void_p), ("ldy", C.c_int)]
+
+
 _P, _I, _U64, _U32, _F, _SZ =C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_size_t
 _SIGS = {
     "llmi_last_error": (C.c_char_p, []),
@@ -141,6 +149,8 @@ _SIGS = {
                                           C.POINTER(_I), C.POINTER(_I)]),
     "llmi_debug_gemm": (_I, [C.POINTER(DebugGemmArgs), _P]),
     "llmi_debug_gemm_plan": (_I, [C.POINTER(DebugGemmArgs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "llmi_debug_gemm1": (_I, [C.POINTER(DebugGemm1Args), _P]),
+    "llmi_debug_gemm1_plan": (_I, [C.POINTER(DebugGemm1Args), C.POINTER(_I), C.POINTER(_I)]),
     "llmi_debug_rows_split": (_I, [_P, _I, _I, _I, _P, _I, _F, _P, _P, _I, _P, _I, _I, _P]),
     "llmi_debug_w8_prepare": (_I, [_P, _I, _I, _P, C.POINTER(_I), _P]),
     "llmi_hbm_read_bench": (_I, [_SZ, _I, _P, _P, _P]),

@@ -622,6 +622,23 @@ def debug_gemm_plan(**fields):
     return tuple(o.value for o in out)
 
 
+def debug_gemm1(**fields) -> None:
+    """llmi_debug_gemm1 (test hook): one launch of the first-generation prefill GEMM (gemm.hip)
+    with llmi_debug_gemm1_args filled from the keywords (tensors become their device addresses;
+    the rest stays zero)."""
+    a = _debug_args(_lib.DebugGemm1Args, fields)
+    call("llmi_debug_gemm1", ctypes.byref(a), _stream())
+
+
+def debug_gemm1_plan(**fields):
+    """llmi_debug_gemm1_plan (test hook): (bm, grid) that debug_gemm1 would run for the same
+    keywords; launches and allocates nothing."""
+    a = _debug_args(_lib.DebugGemm1Args, fields)
+    out = [ctypes.c_int(0) for _ in range(2)]
+    call("llmi_debug_gemm1_plan", ctypes.byref(a), *[ctypes.byref(o) for o in out])
+    return tuple(o.value for o in out)
+
+
 def debug_rows_split(x, m: int, k: int, hi=None, lo=None, ldx: int = 0, ldh: int = 0, gamma=None,
                      eps: float = 1e-5, slab=None, ksplit: int = 0, lo8: bool = False) -> None:
     """llmi_debug_rows_split (test hook): rows_split_launch on device tensors (ldx / ldh 0: k)."""

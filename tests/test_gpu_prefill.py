@@ -1,5 +1,7 @@
-"""Prefill path on the MI355X: the MFMA GEMM
-(gemm.hip) through launchLinearGemm with M > 8 rows, and the engine's batched
+"""Prefill path on the MI355X: the MFMA GEMMs
+through launchLinearGemm with M > 8 rows (fp16 weights with M >= 16: gemm2.hip /
+gemm3.hip, which llmi_linear asks first; int8 weights, and fp16 with 9 <= M < 16:
+gemm.hip, whose operator tests are tests/test_gpu_gemm1.py), and the engine's batched
 prompt pass (llmi_engine_prefill = Llama<T>::firstTokenGen) against the
 reference's f6 fixture (modeling_llama.py, seq 512) and against the engine's own
 token-by-token decode of the same prompt.
@@ -49,7 +51,8 @@ def ops():
 # ------------------------------------------------------------------ GEMM
 def test_gemm_integer_exact_lane_map(ops):
     """Small integers: every product and sum is exact in fp32, so any lane-map or
-    tile-index error shows as a mismatch (asymmetric operands, ragged M)."""
+    tile-index error shows as a mismatch (asymmetric operands, ragged M). fp16 weights at
+    M = 77: llmi_linear runs this through rows_split and gemm2.hip, not gemm.hip."""
     rng = np.random.default_rng(1)
     m, n, k = 77, 256, 192
     x = rng.integers(-4, 5, (m, k)).astype(np.float32)
@@ -61,6 +64,8 @@ def test_gemm_integer_exact_lane_map(ops):
 @pytest.mark.parametrize("m,n,k", [(512, 4096, 4096), (512, 384, 11008), (9, 128, 64), (130, 1536, 512),
                                    (1000, 256, 4096)])
 def test_gemm_f16_fp32_faithful(ops, m, n, k):
+    """llmi_linear with fp16 weights: every shape with M >= 16 runs gemm2.hip / gemm3.hip (planes
+    from rows_split); only (9, 128, 64) still reaches gemm.hip."""
     rng = np.random.default_rng(m + n + k)
     x = rng.standard_normal((m, k)).astype(np.float32)
     w = prng.linear_fp16(5, prng.layer_tid(0, prng.KIND_Q), n, k)

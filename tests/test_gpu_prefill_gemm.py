@@ -44,8 +44,8 @@ lo8 kernel 7.367e-6 against the unsplit product with the planes' model at 7.365e
 alone: 2.1e-4); C fp32 y max row 4.7e-8, the numpy restatement's own figure.
 
 Not covered (not reachable from any caller, not exposed by the hook): w_kblock != 0 (head-major
-W blocks), gemm3_silu_bal_kernel (bal_slab is never set), and gemm.hip, the first-generation GEMM
-of the int8 engines."""
+W blocks) and gemm3_silu_bal_kernel (bal_slab is never set). gemm.hip, the first-generation GEMM
+of the int8 engines, has its own file: tests/test_gpu_gemm1.py."""
 import functools
 
 import numpy as np

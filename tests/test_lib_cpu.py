@@ -248,6 +248,80 @@ def test_debug_gemm_plan_reports_the_launchers_choices():
     assert _gemm_plan(**dict(g3, epi=EPI_SLAB, slab=F, ksplit=2, **lo8)) == (256, 4, 0)  # one fp8 tile a slice
 
 
+# (m, n, k, epi) of tests/test_gpu_gemm1.py: sections A (the m x k walk, the four forms, add), B, C, D, E, F
+_G1_M, _G1_N, _G1_K = (1, 63, 64, 65, 130), (128, 256, 384), (64, 128, 192, 320)
+GEMM1_FORMS = [(129, 16384, 64, 128, 256), (257, 11008, 64, 128, 258), (64, 1024, 128, 64, 8), (65, 384, 128, 64, 6)]
+GEMM1_SHAPES = \
+    [(m, _G1_N[(i + j) % 3], k, EPI_STORE) for i, m in enumerate(_G1_M) for j, k in enumerate(_G1_K)] + \
+    [(m, n, k, EPI_STORE) for m, n, k, _, _ in GEMM1_FORMS] + \
+    [(m, n, k, EPI_ADD) for m, n, k in ((65, 256, 192), (130, 128, 64), (129, 16384, 64))] + \
+    [(m, n, k, e) for m, n, k in ((130, 256, 320), (129, 16384, 128)) for e in (EPI_STORE, EPI_ADD)] + \
+    [(130, 256, 320, EPI_STORE), (257, 11008, 192, EPI_STORE), (130, 2 * 128, 320, EPI_SILU),
+     (129, 2 * 8192, 192, EPI_SILU)] + \
+    [(m, 2 * i, k, EPI_SILU) for m, i, k in ((65, 64, 128), (130, 128, 64), (1, 192, 192), (129, 8192, 64))] + \
+    [(64, 128, 1024, EPI_STORE), (130, 256, 192, EPI_STORE), (9, 128, 64, EPI_STORE)]
+
+
+def _gemm1_plan(**kw):
+    F = 0x1000  # never dereferenced
+    a = _lib.DebugGemm1Args()
+    base = dict(a=F, w=F, y=F, w_dtype=_lib.F16, m=64, n=256, k=128, split=2, eps=1e-5)
+    kw = dict(base, **kw)
+    if kw.get("epi") == EPI_SILU:
+        kw.setdefault("gamma", F)
+        kw.setdefault("g_dtype", _lib.F16)
+    kw.setdefault("lda", kw["k"])
+    kw.setdefault("ldy", kw["n"] // 2 if kw.get("epi") == EPI_SILU else kw["n"])
+    for key, v in kw.items():
+        setattr(a, key, v)
+    o = [C.c_int() for _ in range(2)]
+    call("llmi_debug_gemm1_plan", C.byref(a), *[C.byref(x) for x in o])
+    return tuple(x.value for x in o)
+
+
+def _gemm1_model(m, n, k, epi):
+    """gemm.hip's rule restated: 128 columns a tile (gate_up: 64 gate columns), rows by 128 iff
+    ceil(m / 128) x column tiles >= 256, else by 64; one workgroup per tile."""
+    nt = (n // 2) // 64 if epi == EPI_SILU else n // 128
+    bm = 128 if -(-m // 128) * nt >= 256 else 64
+    return bm, -(-m // bm) * nt
+
+
+def test_debug_gemm1_plan_reports_the_launchers_choices():
+    """llmi_debug_gemm1_plan launches and allocates nothing. bm and grid of every shape of
+    tests/test_gpu_gemm1.py against the rule restated above (both weight types, both splits: the
+    plan does not depend on them), the four forms by hand, then every argument check of
+    gemm_plan."""
+    F = 0x1000
+    for m, n, k, epi in GEMM1_SHAPES:
+        for wt, split in ((_lib.F16, 2), (_lib.I8, 1)):
+            kw = dict(m=m, n=n, k=k, epi=epi, w_dtype=wt, scales=F, split=split)
+            assert _gemm1_plan(**kw) == _gemm1_model(m, n, k, epi), kw
+    for m, n, k, bm, grid in GEMM1_FORMS:
+        assert _gemm1_plan(m=m, n=n, k=k) == (bm, grid)
+    assert _gemm1_plan(m=129, n=2 * 8192, k=64, epi=EPI_SILU) == (128, 256)
+    assert _gemm1_plan(m=128, n=16384, k=64) == (64, 256)                      # 1 x 128 tiles < 256
+    assert _gemm1_plan(m=256, n=11008, k=64) == (64, 4 * 86)                    # 2 x 86 tiles < 256
+    assert _gemm1_plan(m=257, n=4096, k=4096, w_dtype=_lib.I8, scales=F) == (64, 5 * 32)
+    assert _gemm1_plan(m=512, n=3 * 5120, k=5120, w_dtype=_lib.I8, scales=F) == (128, 4 * 120)   # 13B qkv, 512 rows
+    gam = dict(gamma=F, g_dtype=_lib.F16)
+    silu = dict(epi=EPI_SILU, **gam)
+    for bad in (dict(a=0), dict(w=0), dict(y=0), dict(m=0), dict(n=192), dict(k=96), dict(lda=124), dict(lda=130),
+                dict(a=F + 8), dict(w=F + 8), dict(gamma=F + 4, g_dtype=_lib.F16), dict(gamma=F + 8, g_dtype=_lib.F32),
+                dict(gamma=F, g_dtype=_lib.I8), dict(w_dtype=_lib.I8), dict(w_dtype=_lib.F32), dict(split=0),
+                dict(split=3), dict(epi=3), dict(epi=EPI_SLAB), dict(epi=EPI_ADD, **gam), dict(epi=EPI_SILU, gamma=0),
+                dict(silu, n=2 * 96), dict(ldy=255), dict(silu, ldy=127), dict(n=0), dict(k=0)):
+        with pytest.raises(_lib.LlmiError):
+            _gemm1_plan(**bad)
+    # the forms the refusals start from are accepted
+    for ok in (dict(), dict(lda=132), gam, dict(gamma=F + 8, g_dtype=_lib.F16), dict(gamma=F, g_dtype=_lib.F32),
+               dict(w_dtype=_lib.I8, scales=F), dict(split=1), dict(epi=EPI_ADD), dict(ldy=264)):
+        assert _gemm1_plan(**ok) == (64, 2)
+    assert _gemm1_plan(**silu) == (64, 2) and _gemm1_plan(**dict(silu, ldy=128)) == (64, 2)
+    with pytest.raises(_lib.LlmiError):
+        call("llmi_debug_gemm1_plan", None, C.byref(C.c_int()), C.byref(C.c_int()))
+
+
 def test_debug_gemv_plan_reports_the_launchers_choices():
     """llmi_debug_gemv_plan launches nothing, so its ladder is checked without a GPU: the
     x-staging width at each threshold (k / 4 float4s against 4, 5, 11, 14 x 256), the unroll
