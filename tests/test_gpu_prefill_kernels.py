@@ -313,16 +313,25 @@ def ulp_dist16(a, b):
 
 
 ROPE_CASES = [(0, 1), (0, 65), (20, 64), (500, 40)]
+# 40 + 40 heads (Llama-2-13B): 1,280 k/q and 1,280 v work items over the write kernel's 1,024
+# threads, so both of its loops take a second, partly filled pass
+WIDE = (20, 3, 40, 40, 64)   # (p0, m, heads, kv_heads, max_seq)
+
+
+def indexed_case(cases, i, hs):
+    """(p0, m, heads, kv_heads, max_seq): cases[i] on head set hs, or WIDE for the index past the list."""
+    if i == len(cases):
+        return WIDE
+    return cases[i] + HEADSETS[hs % 3] + (None,)
 
 
 @pytest.mark.parametrize("cache", ["f16", "f32"])
 @pytest.mark.parametrize("two", [False, True], ids=["qkv", "qkv+qkv2"])
-@pytest.mark.parametrize("i", range(len(ROPE_CASES)), ids=[f"p{p}m{m}" for p, m in ROPE_CASES])
+@pytest.mark.parametrize("i", range(len(ROPE_CASES) + 1), ids=[f"p{p}m{m}" for p, m in ROPE_CASES] + ["p20m3h40"])
 def test_rope_and_cache_write(ops, i, two, cache):
     """rope_kv_prefill_kernel<__half / float>, with and without the second summand."""
-    p0, m = ROPE_CASES[i]
-    heads, kvh = HEADSETS[(i + two) % 3]
-    c = Case(p0, m, heads, kvh, cache, qkv2=two, seed=1)
+    p0, m, heads, kvh, max_seq = indexed_case(ROPE_CASES, i, i + two)
+    c = Case(p0, m, heads, kvh, cache, qkv2=two, seed=1, max_seq=max_seq)
     r = launch(ops, c)
     pos = p0 + np.arange(m)
     x = c.summed()
@@ -366,12 +375,11 @@ SCALAR_CASES = [(0, 1), (0, 31), (0, 33), (20, 64), (500, 40)]
 
 
 @pytest.mark.parametrize("cache", ["f16", "f32"])
-@pytest.mark.parametrize("i", range(len(SCALAR_CASES)), ids=[f"p{p}m{m}" for p, m in SCALAR_CASES])
+@pytest.mark.parametrize("i", range(len(SCALAR_CASES) + 1), ids=[f"p{p}m{m}" for p, m in SCALAR_CASES] + ["p20m3h40"])
 def test_scalar_attention(ops, i, cache):
     """attn_prefill_kernel<__half / float>: 32-row query blocks, 32-key chunks."""
-    p0, m = SCALAR_CASES[i]
-    heads, kvh = HEADSETS[(i + (cache == "f32")) % 3]
-    c = Case(p0, m, heads, kvh, cache, qkv2=bool(i & 1), seed=2)
+    p0, m, heads, kvh, max_seq = indexed_case(SCALAR_CASES, i, i + (cache == "f32"))
+    c = Case(p0, m, heads, kvh, cache, qkv2=bool(i & 1), seed=2, max_seq=max_seq)
     r = launch(ops, c)
     assert r.plan == (0, 1, -(-m // 32) * heads, 0), r.plan
     e = rowhead_err(r.out, attn_ref(c, r), heads)

@@ -79,6 +79,80 @@ def test_shapes_follow_the_leading_axes():
     np.testing.assert_array_equal(b.reshape(-1), b2)
 
 
+def _rot32(x, pos, tab, order):
+    """The prefill write kernel's fp32 rotation of x [rows, n_heads, 128], restated. plain:
+    a*c - b*s, every operation rounded; fma: fma(a, c, -(b*s)), the product b*s rounded to fp32
+    and the rest computed in float64 and rounded once."""
+    c, s = tab[pos, :, 0][:, None, :], tab[pos, :, 1][:, None, :]
+    a0, a1 = x[..., :64], x[..., 64:]
+    if order == "plain":
+        return np.concatenate([a0 * c - a1 * s, a1 * c + a0 * s], axis=-1)
+    f = np.float64
+    r0 = a0.astype(f) * c.astype(f) - (a1 * s).astype(f)
+    r1 = a1.astype(f) * c.astype(f) + (a0 * s).astype(f)
+    return np.concatenate([r0, r1], axis=-1).astype(np.float32)
+
+
+def test_identity_and_quarter_turn_tables_rotate_exactly_in_both_orders():
+    """What tests/test_gpu_kv8_kernels.py compares the kernel with bitwise, on its own cases."""
+    import test_gpu_kv8_kernels as G
+    for table in ("identity", "quarter"):
+        for p0, m, heads, kvh, two, max_seq in G.write_cases():
+            c = G.Case8(p0, m, heads, kvh, qkv2=two, table=table, max_seq=max_seq)
+            for x in c.parts()[:2]:
+                want = c.exact_rotation(x)
+                for order in ("plain", "fma"):
+                    got = _rot32(x, c.pos, c.tab, order)
+                    assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (c.tag, order)
+
+
+def test_both_fp32_rotation_orders_meet_the_write_caps():
+    """The real-table caps the GPU module holds the kernel to are met by the fp32 expression
+    itself, plain and contracted, on every real-table case of that module (same generator)."""
+    import test_gpu_kv8_kernels as G
+    for c in G.real_table_cases():
+        q, k, _ = c.parts()
+        wk, wks = kv8_ref.quant_rows(G.rotate64(k, c.pos, c.tab).astype(np.float32))
+        for order in ("plain", "fma"):
+            gk, gks = kv8_ref.quant_rows(_rot32(k, c.pos, c.tab, order))
+            nadj, nbytes = G.write_caps(gk, gks, wk, wks, (c.tag, order))
+            rq = G.rel(_rot32(q, c.pos, c.tab, order), G.rotate64(q, c.pos, c.tab))
+            print(f"{c.tag} {order}: {nadj} of {wks.size} rows adjacent, {nbytes} of {wk.size} bytes differ, q {rq:.2e}")
+            assert rq < G.BAR
+
+
+def test_requantising_a_dequantised_row_with_a_full_scale_byte_is_the_identity():
+    """x = q * s with max |q| = 127: amax / 127 = s exactly, so quant_rows(x) = (q, s), over the
+    full range of scale bits (subnormal scales and 65504 included)."""
+    rng = np.random.default_rng(2)
+    sb = rng.integers(1, 0x7BFF + 1, 1000).astype(np.uint16)
+    sb[:4] = [0x0001, 0x03FF, 0x0400, 0x7BFF]
+    q = rng.integers(-127, 128, (1000, 128)).astype(np.int8)
+    q[np.arange(1000), rng.integers(0, 128, 1000)] = np.where(rng.random(1000) < 0.5, 127, -127)
+    x = kv8_ref.dequant(q, sb)
+    assert np.isfinite(x).all()
+    q2, sb2 = kv8_ref.quant_rows(x)
+    np.testing.assert_array_equal(sb2, sb)
+    np.testing.assert_array_equal(q2, q)
+
+
+def test_gpu_module_cache_images_poison_every_row_outside_the_real_range():
+    import test_gpu_kv8_kernels as G
+    images = [G.decode_image(8, 2, ctx, True)[0] for ctx in (1, 2, 65, 256)]
+    images += [G.Case8(p0, m, 12, 4).img for p0, m in G.SCALAR_CASES] + [G.Case8(*G.WIDE[:4], max_seq=G.WIDE[4]).img]
+    for im in images:
+        n = im.n_real
+        for q, s in ((im.kq, im.ks), (im.vq, im.vs)):
+            assert (s[:, n:] == kv8_ref.NAN_BITS).all() and np.isnan(kv8_ref.dequant(q[:, n:], s[:, n:])).all()
+            assert (s[:, :n] != kv8_ref.NAN_BITS).all() and np.isfinite(kv8_ref.dequant(q[:, :n], s[:, :n])).all()
+            assert (q[:, n:] != 0).any() or n == q.shape[1]   # random bytes, not zeros, under the NaN scale
+    # per-row amplitudes: the real rows' scales spread over more than a factor 8 (K) and 32 (V)
+    im = G.decode_image(8, 2, 256, True)[0]
+    for s, spread in ((im.ks, 8.0), (im.vs, 32.0)):
+        f = s[:, :im.n_real].view(np.float16).astype(np.float64)
+        assert f.max() / f.min() > spread
+
+
 def test_tiny_model_int8_kv_is_visible_and_keeps_the_tokens():
     f = np.load(os.path.join(REPO, "tests", "golden", "tiny.npz"), allow_pickle=False)
     seed, prompt = int(f["seed"]), np.asarray(f["prompt"], np.int32)
