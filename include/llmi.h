@@ -855,6 +855,39 @@ int llmi_engine_set_logprobs(llmi_engine* e, int n_top);
  * records that exist (positions stepped + 1, record 0 included), *n_top = the setting. Syncs. */
 int llmi_engine_logprobs(llmi_engine* e, float* tok_lp, int32_t* top_ids, float* top_lp, int n, int* n_valid,
                          int* n_top);
+/* llmi_process_logits inside the token step: one launch after the lm_head and before the
+ * sampler (and after a prefill's last row), in the eager and the captured step alike. For
+ * every id of the raw row, in llmi_process_logits' order and arithmetic: an additive bias (a
+ * -inf bias bans the id), presence / frequency penalties over the ids generated so far --
+ * the history is tokens[prompt_len .. current position], or tokens[0 .. current position]
+ * with count_prompt = 1; ids that llmi_engine_edit forces count as prompt -- and the allowed
+ * set of llmi_engine_set_allowed. The processed row goes to a second buffer (the raw logits
+ * are never written); greedy decoding takes its argmax (value descending, ties to the lower
+ * id), and a sampler set with llmi_engine_set_sampling / llmi_engine_set_sampling_params
+ * samples from the processed row instead of the raw one. Logprobs stay those of the raw row.
+ * bias_ids / bias_values [n_bias]: sparse pairs in host memory, read before the call returns
+ * (n_bias = 0: no bias); ids in [0, vocab) without duplicates, values finite or -inf, the
+ * penalties finite, count_prompt 0 or 1 (LLMI_EINVAL otherwise). Each call replaces the bias
+ * and the penalties of the one before and leaves the allowed set alone; rules are on while a
+ * bias, a non-zero penalty or an allowed set is present, and with all three absent the step
+ * is exactly the step without this call. LLMI_EUNSUPPORTED, with the engine left as it was:
+ * tp_world > 1 or a group rank (only a vocab shard is present), speculation on, the ring
+ * decode mode, vocab > 131072, penalties with max_seq > 65535 (16-bit counters). With rules
+ * on, llmi_engine_set_speculation (k > 0) and llmi_engine_set_decode_mode(1) are refused. */
+int llmi_engine_set_logit_rules(llmi_engine* e, const int32_t* bias_ids, const float* bias_values, int n_bias,
+                                float presence_penalty, float frequency_penalty, int count_prompt);
+/* The allowed set of the rules: every id not in ids [n] (host memory, read before the call
+ * returns; in [0, vocab), LLMI_EINVAL otherwise) gets -inf. n = 0 with null ids removes the
+ * mask; an empty set is impossible (n = 0 with non-null ids: LLMI_EINVAL). Replacing the
+ * contents of a set that is present keeps the captured steps (the bitmap is a fixed engine
+ * buffer updated in stream order), so a caller may change it between replayed steps:
+ * constrained choice, a grammar. Same refusals as llmi_engine_set_logit_rules. */
+int llmi_engine_set_allowed(llmi_engine* e, const int32_t* ids, int n);
+/* Remove bias, penalties and allowed set: rules are off. */
+int llmi_engine_clear_logit_rules(llmi_engine* e);
+/* The processed row of the last step (fp32 [vocab]; n must equal vocab). Syncs. LLMI_EINVAL
+ * while rules are off. */
+int llmi_engine_processed_logits(llmi_engine* e, float* out, int n);
 /* Reset the sequence and stage a prompt (device copy). */
 int llmi_engine_set_prompt(llmi_engine* e, const int32_t* ids, int n);
 /* Run n forward steps (one token each). use_graph: replay the captured hipGraph. */
@@ -1148,6 +1181,16 @@ int llmi_batch_edit(llmi_batch* b, int seq, int keep, const int32_t* ids, int n)
 /* llmi_engine_set_sampling_params for one slot: step = seed + the sampled token's position,
  * row 0, as in the engine. */
 int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_params* p);
+/* llmi_engine_set_logit_rules / _set_allowed / _clear_logit_rules / _processed_logits for one
+ * slot: the rules, the allowed set and the processed row are the slot's own (one launch per
+ * active slot with rules on, before that slot's sampler), bitwise those of an engine running
+ * the sequence alone. Replacing the contents of a slot's allowed set keeps the batch's
+ * captured steps; every other change drops them. LLMI_EINVAL for a seq out of range. */
+int llmi_batch_set_logit_rules(llmi_batch* b, int seq, const int32_t* bias_ids, const float* bias_values, int n_bias,
+                               float presence_penalty, float frequency_penalty, int count_prompt);
+int llmi_batch_set_allowed(llmi_batch* b, int seq, const int32_t* ids, int n);
+int llmi_batch_clear_logit_rules(llmi_batch* b, int seq);
+int llmi_batch_processed_logits(llmi_batch* b, int seq, float* out, int n);
 /* llmi_engine_set_logprobs / llmi_engine_logprobs for one slot: the setting and the records are
  * the slot's own (one launch per active slot with logprobs on, after that slot's sampler), and
  * bitwise those of an engine running the sequence alone. llmi_batch_set_prompt clears only

@@ -14,6 +14,7 @@
 #include <memory>
 #include <string>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "layers.h"
@@ -36,6 +37,24 @@ struct TokenLogprobs {
 };
 
 // records [first, first + count) of the engine (the generated tokens of a Response)
+// sparse (id, value) bias pairs -> llmi_engine_set_logit_rules' flat arrays
+inline void SetLogitRules(llmi_engine* eng, const std::vector<std::pair<int, float>>& bias, float presence,
+                          float frequency, bool count_prompt) {
+    std::vector<int32_t> ids;
+    std::vector<float> vals;
+    for (const auto& b : bias) {
+        ids.push_back(b.first);
+        vals.push_back(b.second);
+    }
+    LLMI_CALL(llmi_engine_set_logit_rules(eng, ids.empty() ? nullptr : ids.data(), vals.empty() ? nullptr : vals.data(),
+                                          (int)ids.size(), presence, frequency, count_prompt ? 1 : 0));
+}
+// an empty list removes the mask
+inline void SetAllowedTokens(llmi_engine* eng, const std::vector<int>& ids) {
+    const std::vector<int32_t> v(ids.begin(), ids.end());
+    LLMI_CALL(llmi_engine_set_allowed(eng, v.empty() ? nullptr : v.data(), (int)v.size()));
+}
+
 inline TokenLogprobs ReadLogprobs(llmi_engine* eng, int first, int count) {
     TokenLogprobs r;
     int valid = 0;
@@ -87,6 +106,16 @@ public:
     // (default), 0 the generated token's, 1..8 also that many alternatives; lastLogprobs reads them
     void setLogprobs(int n_top) { LLMI_CALL(llmi_engine_set_logprobs(eng, n_top)); }
     TokenLogprobs lastLogprobs() { return ReadLogprobs(eng, last_prompt, last_generated); }
+    // logit rules in the token step (llmi_engine_set_logit_rules; no reference counterpart): a bias
+    // per id (-INFINITY bans it), presence / frequency penalties over the generated ids (count_prompt:
+    // the prompt's too), applied before the sampler or the greedy argmax reads the row
+    void setLogitRules(const std::vector<std::pair<int, float>>& bias, float presence = 0, float frequency = 0,
+                       bool count_prompt = false) {
+        SetLogitRules(eng, bias, presence, frequency, count_prompt);
+    }
+    // only these ids may be generated (llmi_engine_set_allowed); an empty list removes the mask
+    void setAllowedTokens(const std::vector<int>& ids) { SetAllowedTokens(eng, ids); }
+    void clearLogitRules() { LLMI_CALL(llmi_engine_clear_logit_rules(eng)); }
 
     // Greedy generation (the reference's K = 1 top-k + sampling). tokens_per_sync
     // forwards run back to back (graph replays) between host reads, so the host
@@ -286,6 +315,15 @@ public:
         const llmi_sampling_params p{top_k, top_p, temperature, repetition_penalty, seed};
         LLMI_CALL(llmi_engine_set_sampling_params(eng, &p));
     }
+
+    // logit rules in the token step (llmi_engine_set_logit_rules / llmi_engine_set_allowed; the
+    // reference has no such control): as LlamaModel's
+    void setLogitRules(const std::vector<std::pair<int, float>>& bias, float presence = 0, float frequency = 0,
+                       bool count_prompt = false) {
+        llm::SetLogitRules(eng, bias, presence, frequency, count_prompt);
+    }
+    void setAllowedTokens(const std::vector<int>& ids) { llm::SetAllowedTokens(eng, ids); }
+    void clearLogitRules() { LLMI_CALL(llmi_engine_clear_logit_rules(eng)); }
 
     // per-token log-probabilities of the pieces Response generates (llmi_engine_set_logprobs: -1
     // off, 0 the token's own, 1..8 also that many alternatives), read by lastLogprobs. The

@@ -312,6 +312,21 @@ struct Engine {
     int32_t* lp_ids() const { return reinterpret_cast<int32_t*>(lp_buf + lp_records() * 4); }
     float* lp_tlp() const { return reinterpret_cast<float*>(lp_buf + lp_records() * 4 * (1 + kLpMaxTop)); }
 
+    // -------------------------------------------------------- logit rules
+    // llmi_engine_set_logit_rules / llmi_engine_set_allowed: one launch (logit_rules.hip, engine
+    // form) after the lm_head and before the sampler, which then reads lr_out instead of logits.
+    // lr_allowed is carved from scratch at setup and holds all ones while no mask is set, so a
+    // mask's contents change with a stream-ordered copy and never with the launch arguments;
+    // lr_bias (dense [vocab]) and lr_out (the processed row [vocab]) are this engine's own
+    // allocations, made by the first setter that needs them and freed in ~Engine.
+    uint32_t* lr_allowed = nullptr;
+    float *lr_bias = nullptr, *lr_out = nullptr;
+    bool lr_bias_on = false, lr_mask_on = false;
+    float lr_presence = 0.f, lr_frequency = 0.f;
+    int lr_count_prompt = 0;
+    size_t lr_words() const { return ((size_t)c.vocab + 31) / 32; }
+    bool rules_on() const { return lr_bias_on || lr_mask_on || lr_presence != 0.f || lr_frequency != 0.f; }
+
     // -------------------------------------------------------- speculation
     // llmi_engine_set_speculation (engine_spec.hip): spec_max extra lanes, each an Engine on this
     // stream that borrows the weights (init's lender) and -- kv_from -- the KV cache and the RoPE
@@ -398,6 +413,14 @@ struct Engine {
     int set_sampling_params(const llmi_sampling_params& p);
     int set_logprobs(int n_top);
     int logprobs_out(float* tok_lp, int32_t* top_ids, float* top_lp, int n, int* n_valid, int* n_top);
+    // ... the logit rules
+    int rules_refusal(const char* who) const;
+    int rules_turn_on();
+    int set_logit_rules(const int32_t* bias_ids, const float* bias_values, int n_bias, float presence, float frequency,
+                        int count_prompt);
+    int set_allowed(const int32_t* ids, int n);
+    int clear_logit_rules();
+    int processed_out(float* out, int n);
     // ... the ring layer
     bool ring_ok() const;
     int set_decode_mode(int mode);

@@ -2,6 +2,7 @@
 // graph, the TP exchange, the ring layer, and the sampling / logprob / option setters.
 // See engine.h.
 #include "engine.h"
+#include "rules_host.h"
 #include "xchg_impl.h"
 
 namespace llmi {
@@ -210,12 +211,21 @@ int Engine::rec_sample() {
     LLMI_TRY(rec_pick());
     return rec_logprob();
 }
+// With logit rules on, their launch comes first: it leaves the processed row in lr_out and its
+// argmax as the only non-zero partial (the greedy pick), and a sampler then reads lr_out.
 int Engine::rec_pick() {
+    const float* row = logits;
+    if (rules_on()) {
+        LLMI_TRY(engine_logit_rules_launch(st, logits, c.vocab, lr_bias_on ? lr_bias : nullptr, lr_allowed, tokens,
+                                           lr_count_prompt, lr_presence, lr_frequency, lr_out, partials, lm_grid,
+                                           stream));
+        row = lr_out;
+    }
     if (nuc_on)
-        return engine_nucleus_launch(st, logits, c.vocab, tokens, nuc.repetition_penalty, nuc.temperature,
+        return engine_nucleus_launch(st, row, c.vocab, tokens, nuc.repetition_penalty, nuc.temperature,
                                      nuc.top_k, nuc.top_p, nuc.seed, partials, lm_grid, stream);
     if (sample_k == 0) return LLMI_OK;
-    LLMI_TRY(topk_launch(logits, LLMI_F32, 1, c.vocab, sample_k, samp_ids, samp_vals, stream));
+    LLMI_TRY(topk_launch(row, LLMI_F32, 1, c.vocab, sample_k, samp_ids, samp_vals, stream));
     return sample_pick_launch(st, samp_ids, samp_vals, sample_k, sample_seed, partials, lm_grid, stream);
 }
 // record cur_pos + 1: the raw row's logprob of the token step_start will pick there (the
@@ -389,6 +399,111 @@ int Engine::logprobs_out(float* tok_lp, int32_t* top_ids, float* top_lp, int n, 
     return LLMI_OK;
 }
 
+// ------------------------------------------------------------ logit rules
+// Rules are on while a bias, a non-zero penalty or an allowed set is present. The host logic
+// that reads the caller's arrays is rules_host.h (checked under sanitizers on the CPU); here
+// its results go to the engine's own device buffers with stream-ordered copies that have
+// completed before the call returns, so no caller pointer and no host vector outlives it.
+// A refused call has changed nothing.
+int Engine::rules_refusal(const char* who) const {
+    const char* why = nullptr;
+    if (c.tp_world != 1 || grouped) why = "the rules need the full logits row (tp_world 1, no group rank)";
+    else if (spec_max > 0) why = "speculation is on (the verify step applies no rules; set_speculation 0 first)";
+    else if (decode_mode == 1) why = "the ring decode mode is on (set_decode_mode 0 first)";
+    if (!why) return LLMI_OK;
+    set_last_error(std::string("[llmi][ERROR] ") + who + ": " + why);
+    return LLMI_EUNSUPPORTED;
+}
+// the rules launch enters the step, or its arguments change: the processed row's buffer
+// exists from here on, and the captured steps are dropped
+int Engine::rules_turn_on() {
+    if (!lr_out) {
+        LLMI_HIP(hipMalloc(&lr_out, (size_t)c.vocab * 4));
+        LLMI_HIP(hipMemsetAsync(lr_out, 0, (size_t)c.vocab * 4, stream));
+    }
+    LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
+    graphs.clear();
+    return LLMI_OK;
+}
+int Engine::set_logit_rules(const int32_t* bias_ids, const float* bias_values, int n_bias, float presence,
+                            float frequency, int count_prompt) {
+    namespace rh = rules_host;
+    LLMI_REQUIRE(rh::penalty_ok(presence) && rh::penalty_ok(frequency), "set_logit_rules: the penalties must be finite");
+    LLMI_REQUIRE(count_prompt == 0 || count_prompt == 1, "set_logit_rules: count_prompt must be 0 or 1");
+    std::vector<float> dense;
+    const int st_ = rh::bias_to_dense(bias_ids, bias_values, n_bias, c.vocab, &dense);
+    LLMI_REQUIRE(st_ == rh::kOk, std::string("set_logit_rules: ") + rh::message(st_));
+    const bool pen = presence != 0.f || frequency != 0.f;
+    if (n_bias > 0 || pen) {
+        LLMI_TRY(rules_refusal("set_logit_rules"));
+        LLMI_TRY(engine_logit_rules_check(c.vocab, c.max_seq, presence, frequency));
+    }
+    if (n_bias == 0 && !pen && !rules_on()) return LLMI_OK;  // off stays off: nothing to record
+    if (n_bias > 0 && !lr_bias) LLMI_HIP(hipMalloc(&lr_bias, (size_t)c.vocab * 4));
+    LLMI_TRY(rules_turn_on());  // (synchronises and clears the graphs: the launch arguments change)
+    if (n_bias > 0) {
+        LLMI_HIP(hipMemcpyAsync(lr_bias, dense.data(), (size_t)c.vocab * 4, hipMemcpyHostToDevice, stream));
+        LLMI_HIP(hipStreamSynchronize(stream));  // dense is read until here
+    }
+    lr_bias_on = n_bias > 0;
+    lr_presence = presence;
+    lr_frequency = frequency;
+    lr_count_prompt = count_prompt;
+    return LLMI_OK;
+}
+// n = 0 with null ids removes the mask. Replacing the contents of a mask that is present leaves
+// the captured steps as they are: the bitmap's address is fixed and the copy is stream-ordered.
+int Engine::set_allowed(const int32_t* ids, int n) {
+    namespace rh = rules_host;
+    LLMI_REQUIRE(n >= 0, "set_allowed: n must be >= 0");
+    LLMI_REQUIRE(n > 0 || !ids, "set_allowed: an empty allowed set (null ids with n = 0 removes the mask)");
+    const bool was_on = rules_on();
+    if (n == 0) {
+        if (!lr_mask_on) return LLMI_OK;
+        LLMI_HIP(hipMemsetAsync(lr_allowed, 0xFF, lr_words() * 4, stream));
+        lr_mask_on = false;
+        if (!rules_on()) {  // the rules launch leaves the captured steps
+            LLMI_HIP(hipStreamSynchronize(stream));
+            graphs.clear();
+        }
+        return LLMI_OK;
+    }
+    std::vector<uint32_t> words;
+    const int st_ = rh::ids_to_bitmap(ids, n, c.vocab, &words);
+    LLMI_REQUIRE(st_ == rh::kOk, std::string("set_allowed: ") + rh::message(st_));
+    if (!was_on) {
+        LLMI_TRY(rules_refusal("set_allowed"));
+        LLMI_TRY(engine_logit_rules_check(c.vocab, c.max_seq, 0.f, 0.f));
+        LLMI_TRY(rules_turn_on());
+    }
+    LLMI_HIP(hipMemcpyAsync(lr_allowed, words.data(), words.size() * 4, hipMemcpyHostToDevice, stream));
+    LLMI_HIP(hipStreamSynchronize(stream));  // words is read until here
+    lr_mask_on = true;
+    return LLMI_OK;
+}
+int Engine::clear_logit_rules() {
+    if (!rules_on()) return LLMI_OK;
+    LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
+    graphs.clear();                          // the captured step changes
+    if (lr_mask_on) {
+        LLMI_HIP(hipMemsetAsync(lr_allowed, 0xFF, lr_words() * 4, stream));
+        LLMI_HIP(hipStreamSynchronize(stream));
+    }
+    lr_bias_on = lr_mask_on = false;
+    lr_presence = lr_frequency = 0.f;
+    lr_count_prompt = 0;
+    return LLMI_OK;
+}
+// the processed row of the last step (what the sampler, or the argmax, chose from)
+int Engine::processed_out(float* out, int n) {
+    LLMI_REQUIRE(out, "processed_logits: null out");
+    LLMI_REQUIRE(n == c.vocab, "processed_logits: n must be the vocabulary size");
+    LLMI_REQUIRE(rules_on() && lr_out, "processed_logits: the logit rules are off");
+    LLMI_HIP(hipStreamSynchronize(stream));
+    LLMI_HIP(hipMemcpy(out, lr_out, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return LLMI_OK;
+}
+
 // ------------------------------------------------ persistent ring layer (mode 1)
 bool Engine::ring_ok() const {
     // layers >= 2: a launch zeroes the NEXT launch's counter block ((l + 1) % L), which for
@@ -405,6 +520,11 @@ int Engine::set_decode_mode(int mode) {
     }
     if (mode == 1 && spec_max > 0) {
         set_last_error("[llmi][ERROR] set_decode_mode: speculation is on (the ring layer has no verify step)");
+        return LLMI_EUNSUPPORTED;
+    }
+    if (mode == 1 && rules_on()) {
+        set_last_error("[llmi][ERROR] set_decode_mode: logit rules are on (not built into the ring mode; "
+                       "clear_logit_rules first)");
         return LLMI_EUNSUPPORTED;
     }
     if (mode == 1) {

@@ -154,6 +154,31 @@ int llmi_engine_logprobs(llmi_engine* e, float* tok_lp, int32_t* top_ids, float*
     return e->e.logprobs_out(tok_lp, top_ids, top_lp, n, n_valid, n_top);
 }
 
+int llmi_engine_set_logit_rules(llmi_engine* e, const int32_t* bias_ids, const float* bias_values, int n_bias,
+                                float presence_penalty, float frequency_penalty, int count_prompt) {
+    LLMI_REQUIRE(e, "engine_set_logit_rules: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.set_logit_rules(bias_ids, bias_values, n_bias, presence_penalty, frequency_penalty, count_prompt);
+}
+
+int llmi_engine_set_allowed(llmi_engine* e, const int32_t* ids, int n) {
+    LLMI_REQUIRE(e, "engine_set_allowed: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.set_allowed(ids, n);
+}
+
+int llmi_engine_clear_logit_rules(llmi_engine* e) {
+    LLMI_REQUIRE(e, "engine_clear_logit_rules: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.clear_logit_rules();
+}
+
+int llmi_engine_processed_logits(llmi_engine* e, float* out, int n) {
+    LLMI_REQUIRE(e, "engine_processed_logits: null engine");
+    LLMI_HIP(hipSetDevice(e->e.device));
+    return e->e.processed_out(out, n);
+}
+
 int llmi_engine_set_prompt(llmi_engine* e, const int32_t* ids, int n) {
     LLMI_REQUIRE(e, "null engine");
     LLMI_HIP(hipSetDevice(e->e.device));
@@ -571,6 +596,42 @@ int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_p
     LLMI_HIP(hipSetDevice(b->b.r[0]->device));
     LLMI_TRY(b->b.r[seq]->set_sampling_params(*p));
     return b->b.drop_graphs();  // the captured steps change
+}
+
+// The slot's own engine setters; the batch's captured steps are dropped wherever the engine
+// form clears its graphs (always for the rules, for a mask only when it turns the rules on or off).
+int llmi_batch_set_logit_rules(llmi_batch* b, int seq, const int32_t* bias_ids, const float* bias_values, int n_bias,
+                               float presence_penalty, float frequency_penalty, int count_prompt) {
+    LLMI_REQUIRE(b, "batch_set_logit_rules: null batch");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    LLMI_TRY(b->b.r[seq]->set_logit_rules(bias_ids, bias_values, n_bias, presence_penalty, frequency_penalty,
+                                          count_prompt));
+    return b->b.drop_graphs();
+}
+
+int llmi_batch_set_allowed(llmi_batch* b, int seq, const int32_t* ids, int n) {
+    LLMI_REQUIRE(b, "batch_set_allowed: null batch");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    const bool was_on = b->b.r[seq]->rules_on();
+    LLMI_TRY(b->b.r[seq]->set_allowed(ids, n));
+    return b->b.r[seq]->rules_on() != was_on ? b->b.drop_graphs() : LLMI_OK;
+}
+
+int llmi_batch_clear_logit_rules(llmi_batch* b, int seq) {
+    LLMI_REQUIRE(b, "batch_clear_logit_rules: null batch");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    LLMI_TRY(b->b.r[seq]->clear_logit_rules());
+    return b->b.drop_graphs();
+}
+
+int llmi_batch_processed_logits(llmi_batch* b, int seq, float* out, int n) {
+    LLMI_REQUIRE(b, "batch_processed_logits: null batch");
+    LLMI_TRY(b->b.slot_ok(seq));
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    return b->b.r[seq]->processed_out(out, n);
 }
 
 int llmi_batch_set_logprobs(llmi_batch* b, int seq, int n_top) {

@@ -186,6 +186,7 @@ const char* Engine::spec_refusal() const {
     if (decode_mode == 1) return "the ring decode mode has no verify step (set_decode_mode 0)";
     if (sample_k > 0 || nuc_on) return "a sampler is active (speculative sampling is not built; greedy only)";
     if (lp_top >= 0) return "logprobs are on (the verify step records none)";
+    if (rules_on()) return "logit rules are on (the verify step applies none; clear_logit_rules first)";
     return nullptr;
 }
 

@@ -9,6 +9,8 @@ Engine::~Engine() {  // teardown errors are not actionable; ignore them explicit
     if (lp_buf) (void)hipFree(lp_buf);
     if (samp_ids) (void)hipFree(samp_ids);
     if (samp_vals) (void)hipFree(samp_vals);
+    if (lr_bias) (void)hipFree(lr_bias);  // (lr_allowed is part of scratch)
+    if (lr_out) (void)hipFree(lr_out);
     graphs.clear();
     clear_spec_graphs();
     lanes.clear();  // the verify lanes before what they borrow
@@ -193,8 +195,11 @@ int Engine::alloc_state() {
     const size_t o_pr = b.take((size_t)c.max_seq * 4), o_tok = b.take((size_t)(c.max_seq + 1) * 4);
     const size_t o_rope = b.take((size_t)c.max_seq * c.head_dim * 4);
     const size_t o_qtag = b.take((size_t)(ql + 2 * kvrows) * 8);
+    const size_t o_lra = b.take(lr_words() * 4);
     LLMI_HIP(hipMalloc(&scratch, b.off));
     LLMI_HIP(hipMemsetAsync(scratch, 0, b.off, stream));
+    lr_allowed = (uint32_t*)(scratch + o_lra);  // the allowed bitmap of the logit rules: all ones = no mask
+    LLMI_HIP(hipMemsetAsync(lr_allowed, 0xFF, lr_words() * 4, stream));
     attn_ws = scratch + o_ws;
     st = (DecodeState*)(scratch + o_st);
     x = (float*)(scratch + o_x);

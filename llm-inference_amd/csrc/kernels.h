@@ -595,6 +595,13 @@ int engine_logprob_rows_launch(const float* slab, int rows, int vocab, const int
 int logit_rules_launch(const float* logits, int rows, int vocab, const float* bias, const uint32_t* allowed,
                        int allowed_stride, const int32_t* history, int history_stride, const int32_t* history_len,
                        float presence, float frequency, float* out, int32_t* out_ids, hipStream_t s);
+// engine form: one row, the history tokens[h0 .. cur_pos] from the device state (h0 = 0 when
+// count_prompt, else prompt_len), `allowed` always present (all ones = no mask), the winner left
+// as the only non-zero argmax partial (as sample_pick_launch); logits, bias and out 16-byte aligned
+int engine_logit_rules_check(int vocab, int max_seq, float presence, float frequency);
+int engine_logit_rules_launch(const struct DecodeState* st, const float* logits, int vocab, const float* bias,
+                              const uint32_t* allowed, const int32_t* tokens, int count_prompt, float presence,
+                              float frequency, float* out, unsigned long long* partials, int np, hipStream_t s);
 int repeat_kv_launch(const void* k_cache, const void* v_cache, int dtype, int layer, const int* ctx_len, int batch,
                      int kv_heads, int max_seq, int heads, int max_k_len, int d, void* k_dst, void* v_dst,
                      hipStream_t s);

@@ -180,6 +180,14 @@ _SIGS = {
     "llmi_engine_set_sampling_params": (_I, [_P, _P]),
     "llmi_engine_set_logprobs": (_I, [_P, _I]),
     "llmi_engine_logprobs": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I), C.POINTER(_I)]),
+    "llmi_engine_set_logit_rules": (_I, [_P, _P, _P, _I, _F, _F, _I]),
+    "llmi_engine_set_allowed": (_I, [_P, _P, _I]),
+    "llmi_engine_clear_logit_rules": (_I, [_P]),
+    "llmi_engine_processed_logits": (_I, [_P, _P, _I]),
+    "llmi_batch_set_logit_rules": (_I, [_P, _I, _P, _P, _I, _F, _F, _I]),
+    "llmi_batch_set_allowed": (_I, [_P, _I, _P, _I]),
+    "llmi_batch_clear_logit_rules": (_I, [_P, _I]),
+    "llmi_batch_processed_logits": (_I, [_P, _I, _P, _I]),
     "llmi_engine_load_tensor": (_I, [_P, C.c_char_p, _P, _SZ]),
     "llmi_engine_load_bin_quantized": (_I, [_P, C.c_char_p]),
     "llmi_engine_load_tensor_quantized": (_I, [_P, C.c_char_p, _P, _SZ]),

@@ -61,6 +61,67 @@ def _read_logprobs(fn: str, handle: tuple, n: int):
     return lp, ids, tlp
 
 
+def _bias_pairs(bias):
+    """(ids int32 [n], values fp32 [n]) of a logit bias given as a dict {id: value} or as a dense
+    array (its non-zero entries; a NaN entry is kept, for the library to refuse)."""
+    if bias is None:
+        return np.zeros(0, np.int32), np.zeros(0, np.float32)
+    if isinstance(bias, dict):
+        ids = np.array([int(k) for k in bias], np.int32).reshape(-1)
+        vals = np.array([float(bias[k]) for k in bias], np.float32).reshape(-1)
+        return ids, vals
+    dense = np.ascontiguousarray(bias, np.float32)
+    if dense.ndim != 1:
+        raise ValueError("bias: a dict {id: value} or a one-dimensional array")
+    ids = np.flatnonzero(dense != 0).astype(np.int32)
+    return ids, np.ascontiguousarray(dense[ids])
+
+
+def _set_rules(fn: str, handle: tuple, bias, presence_penalty, frequency_penalty, count_prompt):
+    ids, vals = _bias_pairs(bias)
+    call(fn, *handle, ids.ctypes.data if len(ids) else None, vals.ctypes.data if len(ids) else None, len(ids),
+         float(presence_penalty), float(frequency_penalty), 1 if count_prompt else 0)
+
+
+def _set_allowed(fn: str, handle: tuple, ids):
+    """Returns the set as the wrapper remembers it (None: no mask)."""
+    if ids is None:
+        call(fn, *handle, None, 0)
+        return None
+    ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+    if len(ids) == 0:
+        raise ValueError("set_allowed: an empty allowed set (None removes the mask)")
+    call(fn, *handle, ids.ctypes.data, len(ids))
+    return ids.copy()
+
+
+def choice_trie(choices) -> list:
+    """The trie of constrained choice over token-id sequences: nodes {"next": {id: node},
+    "leaf": choice index or -1}, node 0 the root. ValueError for no choice, an empty choice,
+    duplicates, and a choice that is a prefix of another (the walk could not tell them apart)."""
+    if len(choices) == 0:
+        raise ValueError("choose: no choices")
+    nodes = [{"next": {}, "leaf": -1}]
+    for k, ch in enumerate(choices):
+        ch = [int(t) for t in ch]
+        if not ch:
+            raise ValueError("choose: an empty choice")
+        at = 0
+        for t in ch:
+            if nodes[at]["leaf"] >= 0:
+                raise ValueError("choose: a choice is a prefix of another")
+            if t not in nodes[at]["next"]:
+                nodes[at]["next"][t] = len(nodes)
+                nodes.append({"next": {}, "leaf": -1})
+            at = nodes[at]["next"][t]
+        if nodes[at]["leaf"] >= 0:
+            raise ValueError("choose: duplicate choices")
+        if nodes[at]["next"]:
+            raise ValueError("choose: a choice is a prefix of another")
+        nodes[at]["leaf"] = k
+    return nodes
+
+
 class Engine:
     def __init__(self, cfg: Config, device: int = 0, tp_id: Optional[bytes] = None):
         self.cfg = cfg
@@ -69,6 +130,7 @@ class Engine:
         call("llmi_engine_create", C.byref(cfg), device, idbuf, C.byref(h))
         self._h = h
         self._lp_top = -1
+        self._allowed = None  # the allowed set as last given to set_allowed (None: no mask)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -116,6 +178,58 @@ class Engine:
         forward at p - 1; NaN / id -1 = not computed (record 0, and prompt rows a batched prefill
         consumed)."""
         return _read_logprobs("llmi_engine_logprobs", (self._h,), self.cfg.max_seq + 1 if n is None else int(n))
+
+    def set_logit_rules(self, bias=None, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                        count_prompt: bool = False):
+        """Logit rules in the token step (llmi_engine_set_logit_rules), applied to every row before
+        the sampler (or the greedy argmax) reads it: bias, a dict {id: value} or a dense array
+        (value -inf bans the id); presence / frequency penalties over the ids generated so far
+        (count_prompt: the prompt's too). Replaces the bias and penalties set before and leaves
+        the allowed set alone; all defaults = none of the three."""
+        _set_rules("llmi_engine_set_logit_rules", (self._h,), bias, presence_penalty, frequency_penalty, count_prompt)
+
+    def set_allowed(self, ids):
+        """Only these ids may be chosen (llmi_engine_set_allowed); None removes the mask. Cheap
+        to change between steps: a replayed graph keeps working."""
+        self._allowed = _set_allowed("llmi_engine_set_allowed", (self._h,), ids)
+
+    def clear_logit_rules(self):
+        """Remove bias, penalties and the allowed set (llmi_engine_clear_logit_rules)."""
+        call("llmi_engine_clear_logit_rules", self._h)
+        self._allowed = None
+
+    def processed_logits(self) -> np.ndarray:
+        """The row the last step chose from, after the rules (llmi_engine_processed_logits)."""
+        out = np.zeros(self.cfg.vocab, np.float32)
+        call("llmi_engine_processed_logits", self._h, out.ctypes.data, self.cfg.vocab)
+        return out
+
+    def choose(self, prompt, choices, use_graph: bool = True):
+        """Constrained choice: after `prompt`, generate exactly one of `choices` (token-id
+        sequences), each token picked by the engine (its rules and sampler included) among the
+        ids that keep a choice reachable. Returns (index of the choice, its ids). Walks the trie
+        of the choices: set_allowed(children) before the step that picks the next token, one
+        decode step, read the token. The allowed set in force before the call is restored."""
+        nodes = choice_trie(choices)
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32).reshape(-1)
+        before = self._allowed
+        try:
+            self.set_prompt(prompt)
+            if len(prompt) > 1:
+                self.decode(len(prompt) - 1, use_graph)  # (their picks are the prompt's: no mask needed)
+            at, ids = 0, []
+            while nodes[at]["leaf"] < 0:
+                self.set_allowed(sorted(nodes[at]["next"]))
+                self.decode(1, use_graph)
+                p = len(prompt) + len(ids)
+                tok = int(self.tokens(p + 1)[p])
+                if tok not in nodes[at]["next"]:
+                    raise _lib.LlmiError(f"choose: the engine picked id {tok} outside the allowed set")
+                ids.append(tok)
+                at = nodes[at]["next"][tok]
+            return nodes[at]["leaf"], ids
+        finally:
+            self.set_allowed(before)
 
     def score(self, ids, use_graph: bool = True, prefill: bool = False, exact=True) -> np.ndarray:
         """Log-likelihood of a given text: logprob of ids[p] given ids[:p] for p = 1 .. len - 1
@@ -490,6 +604,24 @@ class Batch:
                             repetition_penalty: float = 1.0, seed: int = 0):
         p = _lib.SamplingParams(int(top_k), float(top_p), float(temperature), float(repetition_penalty), int(seed))
         call("llmi_batch_set_sampling_params", self._h, int(seq), C.byref(p))
+
+    def set_logit_rules(self, seq: int, bias=None, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                        count_prompt: bool = False):
+        """Engine.set_logit_rules for one slot (the rules and the processed row are the slot's own)."""
+        _set_rules("llmi_batch_set_logit_rules", (self._h, int(seq)), bias, presence_penalty, frequency_penalty,
+                   count_prompt)
+
+    def set_allowed(self, seq: int, ids):
+        """Engine.set_allowed for one slot; replacing a set's contents keeps the captured steps."""
+        _set_allowed("llmi_batch_set_allowed", (self._h, int(seq)), ids)
+
+    def clear_logit_rules(self, seq: int):
+        call("llmi_batch_clear_logit_rules", self._h, int(seq))
+
+    def processed_logits(self, seq: int) -> np.ndarray:
+        out = np.zeros(self.cfg.vocab, np.float32)
+        call("llmi_batch_processed_logits", self._h, int(seq), out.ctypes.data, self.cfg.vocab)
+        return out
 
     def set_logprobs(self, seq: int, n_top: int):
         """Engine.set_logprobs for one slot (the setting and the records are the slot's own)."""
