@@ -149,7 +149,6 @@ int llmi_debug_gemv_rows(const llmi_debug_gemv_args* args, int m, llmi_stream_t 
     LLMI_REQUIRE(args != nullptr, "debug_gemv_rows: null arguments");
     LLMI_REQUIRE(m >= 2 && m <= kGemvRowsMax, "debug_gemv_rows: m must be 2..8");
     GemvRowsArgs p;
-    p.m = m;
     for (int i = 0; i < m; ++i) {
         const llmi_debug_gemv_args& d = args[i];
         const llmi_debug_gemv_args& z = args[0];
@@ -163,12 +162,7 @@ int llmi_debug_gemv_rows(const llmi_debug_gemv_args* args, int m, llmi_stream_t 
                          d.ksplit == z.ksplit && d.yacc_single == z.yacc_single && d.seed_n == z.seed_n &&
                          d.seed_keep == z.seed_keep && d.kpar == z.kpar,
                      "debug_gemv_rows: the rows must share every weight-side, shape and epilogue field");
-        const GemvArgs a = debug_gemv_args(d);
-        if (i == 0) p.a = a;
-        GemvRow& r = p.row[i];
-        r.x = a.x; r.x_fixed = a.x_fixed; r.x_out = a.x_out; r.y = a.y; r.resid = a.resid;
-        r.yacc = a.yacc; r.yacc_base = a.yacc_base; r.yacc_copy = a.yacc_copy; r.partials = a.partials;
-        r.seed_src = a.seed_src; r.seed_dst = a.seed_dst;
+        gemv_rows_add(p, debug_gemv_args(d));
     }
     return gemv_rows_launch(p, STREAM(stream));
 }

@@ -32,6 +32,16 @@
 // next token. Weights are generated shard-by-shard from the same global PRNG
 // indices, so every TP degree computes the same model.
 //
+// Captured steps: who owns them, what invalidates them. Every captured step lives in a
+// GraphCache of the object that launches it: an Engine's token steps (by split count) and its
+// verify steps (by rows and split count), a Group's steps, a Batch's steps (by the active slots
+// and their split counts). A key carries only what changes without a setter call; whatever a
+// setter changes in a recorded step goes through Engine::invalidate(), which drops the engine's
+// own caches and those of the owner whose steps hold this engine's launches (a slot's batch, a
+// verify lane's engine). A Group drops its own cache in Group::set_exchange. Replacing the
+// contents of an allowed-token mask that is already present is a stream-ordered copy into a
+// fixed buffer and invalidates nothing.
+//
 // One struct Engine, defined over several units: engine_weights.hip (setup and the
 // loaders), engine.hip (the token step, the TP exchange, the ring layer, the setters),
 // engine_prefill.hip, engine_spec.hip (the verify step, the lookup and draft-engine loops),
@@ -101,33 +111,70 @@ int capture(hipStream_t s, F&& record, hipGraph_t* graph, hipGraphExec_t* exec) 
     return LLMI_OK;
 }
 
-// The token graphs, one per active split count nact = pos / 64 + 1: the attention
-// and o_proj grids are sized on the host (AttnArgs::nact), so one captured step is
-// valid for 64 consecutive positions. Built lazily, before a decode run's launches.
-struct StepGraphs {
-    std::vector<hipGraph_t> g;
-    std::vector<hipGraphExec_t> x;
-    void clear() {
-        for (auto e : x)
-            if (e) (void)hipGraphExecDestroy(e);
-        for (auto h : g)
-            if (h) (void)hipGraphDestroy(h);
-        x.clear();
-        g.clear();
-    }
-    ~StepGraphs() { clear(); }
-    bool empty() const { return x.empty(); }
-    // capture record() (which records one step for nact) on s unless cached
-    template <typename F>
-    int build(int nact, hipStream_t s, F&& record) {
-        if ((int)x.size() <= nact) {
-            x.resize(nact + 1, nullptr);
-            g.resize(nact + 1, nullptr);
+// The captured steps of one owner (an Engine's token steps and its verify steps, a Group's, a
+// Batch's), by key, built lazily. The attention and o_proj grids are sized on the host
+// (AttnArgs::nact = pos / 64 + 1), so a captured step is valid for 64 consecutive positions and
+// every key carries the split count(s). The cache owns the graphs and their execs. bound > 0: a
+// full cache is dropped whole (after a stream sync) before the next capture.
+template <typename Key>
+struct GraphCache {
+    std::map<Key, std::pair<hipGraph_t, hipGraphExec_t>> m;
+    size_t bound;
+    explicit GraphCache(size_t bound_ = 0) : bound(bound_) {}
+    GraphCache(const GraphCache&) = delete;
+    GraphCache& operator=(const GraphCache&) = delete;
+    ~GraphCache() { clear(); }
+    void clear() {  // (the caller knows that no replay is in flight)
+        for (auto& kv : m) {
+            (void)hipGraphExecDestroy(kv.second.second);
+            (void)hipGraphDestroy(kv.second.first);
         }
-        if (x[nact]) return LLMI_OK;
-        return capture(s, record, &g[nact], &x[nact]);
+        m.clear();
+    }
+    // what every invalidation is: a replay may still be in flight, so synchronise, then clear
+    int drop(hipStream_t s) {
+        if (m.empty()) return LLMI_OK;
+        LLMI_HIP(hipStreamSynchronize(s));
+        clear();
+        return LLMI_OK;
+    }
+    // *exec = the step of `key`, captured with record() on s where the cache has none; a failed
+    // capture leaves no entry (and, capture(): no stream stuck in capture mode)
+    template <typename F>
+    int get(const Key& key, hipStream_t s, F&& record, hipGraphExec_t* exec) {
+        auto it = m.find(key);
+        if (it == m.end()) {
+            if (bound && m.size() >= bound) LLMI_TRY(drop(s));
+            hipGraph_t h = nullptr;
+            hipGraphExec_t x = nullptr;
+            LLMI_TRY(capture(s, record, &h, &x));
+            it = m.emplace(key, std::make_pair(h, x)).first;
+        }
+        *exec = it->second.second;
+        return LLMI_OK;
     }
 };
+using BatchGraphs = GraphCache<std::vector<int>>;
+
+// One multi-row GEMV from the single-row arguments args_of(engine) of up to kGemvRowsMax engines
+// (a batch's active slots, a verify step's lanes): the launch takes the first engine's weights
+// and shape and every engine's own row pointers. with_stamps false: it writes no debug stamps.
+struct Engine;
+template <typename F>
+int gemv_rows_of(const std::vector<Engine*>& es, hipStream_t s, F&& args_of, bool with_stamps = true) {
+    GemvRowsArgs p;
+    for (Engine* e : es) gemv_rows_add(p, args_of(*e));
+    if (!with_stamps) p.a.stamps = nullptr;
+    return gemv_rows_launch(p, s);
+}
+
+// The modes of an engine that refuse one another (Engine::refuse; engine.hip has the table). The
+// first four are fixed when the engine is made; the rest are turned on and off by setters.
+enum Mode { kModeTp, kModeSlot, kModeInt4, kModeKv8, kModeRing, kModeTopK, kModeNucleus, kModeLogprobs, kModeRules,
+            kModeSpec };
+
+// "<n> (1: ..., 2: ...)": a DecodeState::error word and the legend of its bits
+std::string error_flag_text(int flags);
 
 struct Engine {
     llmi_config c{};
@@ -201,7 +248,9 @@ struct Engine {
     int32_t *prompt = nullptr, *tokens = nullptr;
     int host_next_pos = 0, prompt_len = 0;
 
-    StepGraphs graphs;
+    GraphCache<int> graphs;  // the token steps, by split count
+    // a batch slot: the batch's captured steps, which hold this engine's launches (Batch::init)
+    BatchGraphs* owner_graphs = nullptr;
     int rec_nact = 0;  // active split count the next recorded step's attention is sized for
     // fused q/k/v + attention launch (qkv_attn.hip) where the shapes allow it; option "qkv_attn",
     // default LLMI_QKV_ATTN (A/B); qtag: its granule buffer [(heads + 2 kv) * d]
@@ -332,14 +381,14 @@ struct Engine {
     // stream that borrows the weights (init's lender) and -- kv_from -- the KV cache and the RoPE
     // table, with its own DecodeState, x, q/k/v, activations, residual accumulators, attention
     // workspace, logits and argmax partials. spec_draft: device [8] draft ids, then {a, g_a, error}.
-    // spec_graphs: captured verify steps by (rows, split count of the last row); bounded, a full
-    // cache is dropped whole (after a sync) before the next capture
-    const Engine* kv_from = nullptr;
+    // spec_graphs: captured verify steps by (rows, split count of the last row). A lane's
+    // kv_from is its engine, whose verify steps hold the lane's launches.
+    Engine* kv_from = nullptr;
     int spec_max = 0;
     std::vector<std::unique_ptr<Engine>> lanes;
     int32_t* spec_draft = nullptr;
     static constexpr size_t kMaxSpecGraphs = 64;
-    std::map<std::pair<int, int>, std::pair<hipGraph_t, hipGraphExec_t>> spec_graphs;
+    GraphCache<std::pair<int, int>> spec_graphs{kMaxSpecGraphs};
 
     // -------------------------------------------------------------- debug
     unsigned long long* dbg_stamps = nullptr;  // llmi_engine_debug_stamps: per-workgroup timeline
@@ -397,7 +446,8 @@ struct Engine {
     int rec_logprob();
     int record_step();
     static int nact_of(int pos) { return pos / kAttnChunk + 1; }
-    int build_graph(int nact);
+    int build_graph(int nact, hipGraphExec_t* exec);
+    int invalidate();
     int set_prompt(const int32_t* ids, int n);
     int decode(int n, int use_graph);
     int tokens_out(int32_t* out, int n, int* n_valid);
@@ -407,6 +457,11 @@ struct Engine {
     XchgArgs xchg_args(void* buf, int n, int op, int mode) const;
     int exchange(void* buf, int n, int op);
     int set_exchange(int mode);
+    // ... which mode refuses which
+    static unsigned config_modes(const llmi_config& cfg);
+    unsigned modes() const;
+    static int refuse(const char* who, Mode turning_on, unsigned on);
+    int refuse(const char* who, Mode turning_on) const { return refuse(who, turning_on, modes()); }
     // ... the option, sampling and logprob setters
     int set_option(const std::string& name, int value);
     int set_sampling(int k, uint64_t sd);
@@ -414,7 +469,6 @@ struct Engine {
     int set_logprobs(int n_top);
     int logprobs_out(float* tok_lp, int32_t* top_ids, float* top_lp, int n, int* n_valid, int* n_top);
     // ... the logit rules
-    int rules_refusal(const char* who) const;
     int rules_turn_on();
     int set_logit_rules(const int32_t* bias_ids, const float* bias_values, int n_bias, float presence, float frequency,
                         int count_prompt);
@@ -443,11 +497,7 @@ struct Engine {
     int scored_logits_out(int pos, float* out, int n);
 
     // ---- engine_spec.hip: speculative decoding (the verify step, the lookup generation loop)
-    void clear_spec_graphs();
-    const char* spec_refusal() const;
     int set_speculation(int max_draft);
-    template <typename F>
-    int spec_rows(int m, F&& args_of);  // engine_spec.hip, its only user
     int record_verify(int m);
     int verify(const int32_t* draft, int n_draft, int use_graph, int* n_accepted, int* next_token = nullptr);
     int generate_lookup(int n_steps, int max_draft, int ngram_max, int ngram_min, int use_graph,
@@ -474,7 +524,7 @@ struct Group {
     std::vector<std::unique_ptr<Engine>> r;
     hipStream_t stream = nullptr;
     void** ptrs = nullptr;  // device [4][W]: xacc, res[0], res[1], partials of every rank
-    StepGraphs graphs;
+    GraphCache<int> graphs;  // by split count
     // 0: group_reduce_kernel; 1: the one-shot peer exchange's kernels (xchg.hip) -- every
     // rank's push, then every rank's reduce (one stream: the waits find their flags set);
     // 2: the producer-fused form -- every rank's o_proj / down / lm_head launch pushes from
@@ -503,21 +553,17 @@ struct Group {
 struct Batch {
     std::vector<std::unique_ptr<Engine>> r;
     hipStream_t stream = nullptr;
-    // captured steps by key {slot, nact, logprobs, ...} of the active slots; bounded: a full
-    // cache is dropped whole (after a sync) before the next capture
+    // captured steps by key {slot, nact, ...} of the active slots: what changes a step without
+    // a setter call (a slot's setter drops the cache: Engine::invalidate)
     static constexpr size_t kMaxGraphs = 64;
-    std::map<std::vector<int>, std::pair<hipGraph_t, hipGraphExec_t>> graphs;
+    BatchGraphs graphs{kMaxGraphs};
 
-    void clear_graphs();
     ~Batch();
     int init(const llmi_config& cfg, int n_seq, int dev);
     int slot_ok(int seq) const;
-    int drop_graphs();
     int loaded();
     int reset(int seq);
     std::vector<int> active() const;
-    template <typename F>
-    int rows(const std::vector<int>& act, F&& args_of);  // engine_batch.hip, its only user
     int record_step(const std::vector<int>& act);
     int decode(int n, int use_graph);
     int prefill(int seq, int n, int split, bool scored);

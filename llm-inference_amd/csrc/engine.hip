@@ -292,14 +292,104 @@ int Engine::set_exchange(int mode) {
                  "set_exchange: mode must be 0 (RCCL), 1 (one-shot peer exchange) or 2 (fused into the producers)");
     LLMI_REQUIRE(!grouped, "set_exchange: a group rank's exchange is its group's");
     LLMI_REQUIRE(mode == 0 || (inbox && peers_ready), "set_exchange: open the peer exchange first (xchg_open)");
-    LLMI_HIP(hipStreamSynchronize(stream));
-    graphs.clear();  // the captured steps change
+    LLMI_TRY(invalidate());
     xchg_mode = mode;
     tail_mode = mode == 2 ? 3 : 0;
     return LLMI_OK;
 }
+// ------------------------------------------------- captured steps and modes
+// Whatever changes a recorded step's launches or their arguments ends here: this engine's token
+// and verify steps are dropped, and so are the captured steps of the owner that holds this
+// engine's launches (a slot's batch, a verify lane's engine). Each drop synchronises only where
+// there is something to drop: a replay may still be in flight.
+int Engine::invalidate() {
+    LLMI_TRY(graphs.drop(stream));
+    LLMI_TRY(spec_graphs.drop(stream));
+    if (owner_graphs) LLMI_TRY(owner_graphs->drop(stream));
+    return kv_from ? kv_from->invalidate() : LLMI_OK;
+}
+
+// Which mode refuses which: `turning_on` is refused with `why` while `on` is on, the first row
+// that applies. The modes fixed at creation can only be the `on` side. Every pair of modes that
+// setters turn on is listed in both directions (checked below).
+namespace {
+struct Refusal {
+    Mode turning_on, on;
+    int code;
+    const char* why;
+};
+constexpr int kU = LLMI_EUNSUPPORTED, kI = LLMI_EINVAL;
+constexpr Refusal kRefusals[] = {
+    {kModeSlot, kModeTp, kU, "tensor-parallel batches are not built (tp_world must be 1)"},
+    {kModeSlot, kModeInt4, kU, "int4 weights are not built into the multi-row GEMV (use an Engine)"},
+    {kModeTp, kModeInt4, kU, "int4 weights run on a single-rank engine only (no tensor parallel)"},
+    {kModeRing, kModeInt4, kU, "the ring layer streams fp16 weights; int4 engines run mode 0"},
+    {kModeRing, kModeSpec, kU, "speculation is on (the ring layer has no verify step)"},
+    {kModeRing, kModeRules, kU, "logit rules are on (not built into the ring mode; clear_logit_rules first)"},
+    // (the two kI rows keep the condition text that LLMI_REQUIRE appends to such a message)
+    {kModeTopK, kModeTp, kI,
+     "sampling needs the full logits (tp_world 1) (k == 0 || (c.tp_world == 1 && !grouped))"},
+    {kModeTopK, kModeSpec, kU, "speculation is on (greedy only; set_speculation 0 first)"},
+    {kModeNucleus, kModeTp, kI, "sampling needs the full logits (tp_world 1) (c.tp_world == 1 && !grouped)"},
+    {kModeNucleus, kModeSpec, kU, "speculation is on (greedy only; set_speculation 0 first)"},
+    {kModeLogprobs, kModeTp, kU, "logprobs need the full logits row (tp_world 1, no group rank)"},
+    {kModeLogprobs, kModeSpec, kU, "speculation is on (the verify step records none; set_speculation 0 first)"},
+    {kModeRules, kModeTp, kU, "the rules need the full logits row (tp_world 1, no group rank)"},
+    {kModeRules, kModeSpec, kU, "speculation is on (the verify step applies no rules; set_speculation 0 first)"},
+    {kModeRules, kModeRing, kU, "the ring decode mode is on (set_decode_mode 0 first)"},
+    {kModeSpec, kModeTp, kU, "tensor-parallel ranks and group ranks are not built (tp_world must be 1)"},
+    {kModeSpec, kModeInt4, kU, "int4 weights are not built into the multi-row GEMV"},
+    {kModeSpec, kModeKv8, kU, "an int8 KV cache is not built into the multi-row attention"},
+    {kModeSpec, kModeRing, kU, "the ring decode mode has no verify step (set_decode_mode 0)"},
+    {kModeSpec, kModeTopK, kU, "a sampler is active (speculative sampling is not built; greedy only)"},
+    {kModeSpec, kModeNucleus, kU, "a sampler is active (speculative sampling is not built; greedy only)"},
+    {kModeSpec, kModeLogprobs, kU, "logprobs are on (the verify step records none)"},
+    {kModeSpec, kModeRules, kU, "logit rules are on (the verify step applies none; clear_logit_rules first)"},
+};
+constexpr bool refused(Mode turning_on, Mode on) {
+    for (const Refusal& r : kRefusals)
+        if (r.turning_on == turning_on && r.on == on) return true;
+    return false;
+}
+constexpr bool refusals_symmetric() {
+    for (const Refusal& r : kRefusals)
+        if (r.on >= kModeRing && !refused(r.on, r.turning_on)) return false;
+    return true;
+}
+static_assert(refusals_symmetric(), "two modes that setters turn on refuse each other in one direction only");
+}  // namespace
+
+unsigned Engine::config_modes(const llmi_config& cfg) {
+    return (cfg.tp_world != 1 ? 1u << kModeTp : 0) | (cfg.weight_dtype == LLMI_I4 ? 1u << kModeInt4 : 0) |
+           (cfg.kv_dtype == LLMI_I8 ? 1u << kModeKv8 : 0);
+}
+unsigned Engine::modes() const {
+    return config_modes(c) | (grouped ? 1u << kModeTp : 0) | (owner_graphs ? 1u << kModeSlot : 0) |
+           (decode_mode == 1 ? 1u << kModeRing : 0) | (sample_k > 0 ? 1u << kModeTopK : 0) |
+           (nuc_on ? 1u << kModeNucleus : 0) | (lp_top >= 0 ? 1u << kModeLogprobs : 0) |
+           (rules_on() ? 1u << kModeRules : 0) | (spec_max > 0 ? 1u << kModeSpec : 0);
+}
+// `turning_on` while the modes of the bit set `on` are on: LLMI_OK, or the first row's code with
+// "<who>: <why>" as the error text
+int Engine::refuse(const char* who, Mode turning_on, unsigned on) {
+    for (const Refusal& r : kRefusals) {
+        if (r.turning_on != turning_on || !(on >> r.on & 1)) continue;
+        set_last_error(std::string("[llmi][ERROR] ") + who + ": " + r.why);
+        return r.code;
+    }
+    return LLMI_OK;
+}
+
+// The legend of DecodeState::error (kernels.h), the one place it is written out.
+std::string error_flag_text(int flags) {
+    return std::to_string(flags) +
+           " (1: token id out of range, 2: position overflow, 4: attention split count != device position, "
+           "8: a tensor-parallel peer never arrived (one-shot exchange timeout), "
+           "16: a prefill gate_up lo partial never arrived, 32: a ring-layer hand-off timed out, "
+           "64: a fused q/k/v + attention wait timed out)";
+}
+
 int Engine::set_option(const std::string& name, int value) {
-    LLMI_HIP(hipStreamSynchronize(stream));
     if (name == "kpar") {
         LLMI_REQUIRE(value == 0 || value == 1, "set_option kpar: 1 on (default), 0 off");
         kpar_off = value == 0;
@@ -318,39 +408,26 @@ int Engine::set_option(const std::string& name, int value) {
     } else {
         LLMI_REQUIRE(false, "set_option: unknown option (kpar, qkv_attn, qa_o, qa_grid, qa_order, qa_poll)");
     }
-    graphs.clear();  // the captured steps change
-    return LLMI_OK;
+    return invalidate();
 }
 
 int Engine::set_sampling(int k, uint64_t sd) {
     LLMI_REQUIRE(k >= 0 && k <= 16, "set_sampling: k must be in [0, 16] (0 = greedy)");
-    LLMI_REQUIRE(k == 0 || (c.tp_world == 1 && !grouped), "set_sampling: sampling needs the full logits (tp_world 1)");
-    if (k > 0 && spec_max > 0) {
-        set_last_error("[llmi][ERROR] set_sampling: speculation is on (greedy only; set_speculation 0 first)");
-        return LLMI_EUNSUPPORTED;
-    }
+    if (k > 0) LLMI_TRY(refuse("set_sampling", kModeTopK));
     if (k > 0 && !samp_ids) {
         LLMI_HIP(hipMalloc(&samp_ids, 16 * sizeof(int32_t)));
         LLMI_HIP(hipMalloc(&samp_vals, 16 * sizeof(float)));
     }
-    if (!graphs.empty()) {  // the captured step changes: re-capture on the next graph decode
-        LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
-        graphs.clear();
-    }
+    LLMI_TRY(invalidate());
     sample_k = k;
     sample_seed = sd;
     nuc_on = false;  // each of the two setters replaces the other
     return LLMI_OK;
 }
 int Engine::set_sampling_params(const llmi_sampling_params& p) {
-    LLMI_REQUIRE(c.tp_world == 1 && !grouped, "set_sampling_params: sampling needs the full logits (tp_world 1)");
+    LLMI_TRY(refuse("set_sampling_params", kModeNucleus));
     LLMI_TRY(engine_nucleus_check(c.vocab, p.repetition_penalty, p.temperature, p.top_k, p.top_p));
-    if (spec_max > 0) {
-        set_last_error("[llmi][ERROR] set_sampling_params: speculation is on (greedy only; set_speculation 0 first)");
-        return LLMI_EUNSUPPORTED;
-    }
-    LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
-    graphs.clear();                          // the captured step changes
+    LLMI_TRY(invalidate());
     nuc = p;
     nuc_on = true;
     sample_k = 0;
@@ -362,19 +439,10 @@ int Engine::set_sampling_params(const llmi_sampling_params& p) {
 int Engine::set_logprobs(int n_top) {
     LLMI_REQUIRE(n_top >= -1 && n_top <= kLpMaxTop, "set_logprobs: n_top must be -1 (off) or in [0, 8]");
     if (n_top >= 0) {
-        if (c.tp_world != 1 || grouped) {
-            set_last_error("[llmi][ERROR] set_logprobs: logprobs need the full logits row (tp_world 1, no group rank)");
-            return LLMI_EUNSUPPORTED;
-        }
+        LLMI_TRY(refuse("set_logprobs", kModeLogprobs));
         LLMI_TRY(engine_logprob_check(c.vocab, n_top));
-        if (spec_max > 0) {
-            set_last_error("[llmi][ERROR] set_logprobs: speculation is on (the verify step records none; "
-                           "set_speculation 0 first)");
-            return LLMI_EUNSUPPORTED;
-        }
     }
-    LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
-    graphs.clear();                          // the captured step changes
+    LLMI_TRY(invalidate());
     if (n_top >= 0 && !lp_buf) LLMI_HIP(hipMalloc(&lp_buf, lp_bytes()));
     if (n_top >= 0 && n_top != lp_stride) {  // the record stride changes: nothing computed so far is readable
         LLMI_HIP(hipMemsetAsync(lp_buf, 0xFF, lp_bytes(), stream));
@@ -405,15 +473,7 @@ int Engine::logprobs_out(float* tok_lp, int32_t* top_ids, float* top_lp, int n, 
 // its results go to the engine's own device buffers with stream-ordered copies that have
 // completed before the call returns, so no caller pointer and no host vector outlives it.
 // A refused call has changed nothing.
-int Engine::rules_refusal(const char* who) const {
-    const char* why = nullptr;
-    if (c.tp_world != 1 || grouped) why = "the rules need the full logits row (tp_world 1, no group rank)";
-    else if (spec_max > 0) why = "speculation is on (the verify step applies no rules; set_speculation 0 first)";
-    else if (decode_mode == 1) why = "the ring decode mode is on (set_decode_mode 0 first)";
-    if (!why) return LLMI_OK;
-    set_last_error(std::string("[llmi][ERROR] ") + who + ": " + why);
-    return LLMI_EUNSUPPORTED;
-}
+//
 // the rules launch enters the step, or its arguments change: the processed row's buffer
 // exists from here on, and the captured steps are dropped
 int Engine::rules_turn_on() {
@@ -421,9 +481,7 @@ int Engine::rules_turn_on() {
         LLMI_HIP(hipMalloc(&lr_out, (size_t)c.vocab * 4));
         LLMI_HIP(hipMemsetAsync(lr_out, 0, (size_t)c.vocab * 4, stream));
     }
-    LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
-    graphs.clear();
-    return LLMI_OK;
+    return invalidate();
 }
 int Engine::set_logit_rules(const int32_t* bias_ids, const float* bias_values, int n_bias, float presence,
                             float frequency, int count_prompt) {
@@ -435,12 +493,12 @@ int Engine::set_logit_rules(const int32_t* bias_ids, const float* bias_values, i
     LLMI_REQUIRE(st_ == rh::kOk, std::string("set_logit_rules: ") + rh::message(st_));
     const bool pen = presence != 0.f || frequency != 0.f;
     if (n_bias > 0 || pen) {
-        LLMI_TRY(rules_refusal("set_logit_rules"));
+        LLMI_TRY(refuse("set_logit_rules", kModeRules));
         LLMI_TRY(engine_logit_rules_check(c.vocab, c.max_seq, presence, frequency));
     }
     if (n_bias == 0 && !pen && !rules_on()) return LLMI_OK;  // off stays off: nothing to record
     if (n_bias > 0 && !lr_bias) LLMI_HIP(hipMalloc(&lr_bias, (size_t)c.vocab * 4));
-    LLMI_TRY(rules_turn_on());  // (synchronises and clears the graphs: the launch arguments change)
+    LLMI_TRY(rules_turn_on());  // (drops the captured steps: the launch arguments change)
     if (n_bias > 0) {
         LLMI_HIP(hipMemcpyAsync(lr_bias, dense.data(), (size_t)c.vocab * 4, hipMemcpyHostToDevice, stream));
         LLMI_HIP(hipStreamSynchronize(stream));  // dense is read until here
@@ -462,17 +520,13 @@ int Engine::set_allowed(const int32_t* ids, int n) {
         if (!lr_mask_on) return LLMI_OK;
         LLMI_HIP(hipMemsetAsync(lr_allowed, 0xFF, lr_words() * 4, stream));
         lr_mask_on = false;
-        if (!rules_on()) {  // the rules launch leaves the captured steps
-            LLMI_HIP(hipStreamSynchronize(stream));
-            graphs.clear();
-        }
-        return LLMI_OK;
+        return rules_on() ? LLMI_OK : invalidate();  // the rules launch leaves the captured steps
     }
     std::vector<uint32_t> words;
     const int st_ = rh::ids_to_bitmap(ids, n, c.vocab, &words);
     LLMI_REQUIRE(st_ == rh::kOk, std::string("set_allowed: ") + rh::message(st_));
     if (!was_on) {
-        LLMI_TRY(rules_refusal("set_allowed"));
+        LLMI_TRY(refuse("set_allowed", kModeRules));
         LLMI_TRY(engine_logit_rules_check(c.vocab, c.max_seq, 0.f, 0.f));
         LLMI_TRY(rules_turn_on());
     }
@@ -483,8 +537,7 @@ int Engine::set_allowed(const int32_t* ids, int n) {
 }
 int Engine::clear_logit_rules() {
     if (!rules_on()) return LLMI_OK;
-    LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
-    graphs.clear();                          // the captured step changes
+    LLMI_TRY(invalidate());
     if (lr_mask_on) {
         LLMI_HIP(hipMemsetAsync(lr_allowed, 0xFF, lr_words() * 4, stream));
         LLMI_HIP(hipStreamSynchronize(stream));
@@ -513,21 +566,8 @@ bool Engine::ring_ok() const {
 }
 int Engine::set_decode_mode(int mode) {
     LLMI_REQUIRE(mode == 0 || mode == 1, "set_decode_mode: mode must be 0 (launches) or 1 (ring layer)");
-    LLMI_HIP(hipStreamSynchronize(stream));
-    if (mode == 1 && wdt == LLMI_I4) {
-        set_last_error("[llmi][ERROR] set_decode_mode: the ring layer streams fp16 weights; int4 engines run mode 0");
-        return LLMI_EUNSUPPORTED;
-    }
-    if (mode == 1 && spec_max > 0) {
-        set_last_error("[llmi][ERROR] set_decode_mode: speculation is on (the ring layer has no verify step)");
-        return LLMI_EUNSUPPORTED;
-    }
-    if (mode == 1 && rules_on()) {
-        set_last_error("[llmi][ERROR] set_decode_mode: logit rules are on (not built into the ring mode; "
-                       "clear_logit_rules first)");
-        return LLMI_EUNSUPPORTED;
-    }
     if (mode == 1) {
+        LLMI_TRY(refuse("set_decode_mode", kModeRing));
         if (n_cu == 0) LLMI_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
         if (!ring_ok()) {
             set_last_error("[llmi][ERROR] set_decode_mode: the ring layer needs fp16 weights, hidden 4096, "
@@ -542,10 +582,11 @@ int Engine::set_decode_mode(int mode) {
             LLMI_HIP(hipMalloc(&rl_cnt, (size_t)c.layers * kRingCntWords * 4));
             LLMI_HIP(hipMalloc(&wdt_blob, (size_t)c.layers * il * c.hidden * 2));
         }
+        LLMI_HIP(hipStreamSynchronize(stream));  // an eager ring step may still use what is zeroed here
         LLMI_HIP(hipMemset(rl_acc, 0, (size_t)5 * c.hidden * 8));
         LLMI_HIP(hipMemset(rl_cnt, 0, (size_t)c.layers * kRingCntWords * 4));
     }
-    graphs.clear();  // the captured steps change
+    LLMI_TRY(invalidate());
     decode_mode = mode;
     return LLMI_OK;
 }
@@ -615,9 +656,9 @@ int Engine::record_step() {
     return exchange(partials, lm_grid, 2);  // max of the vocab-parallel argmax keys
 }
 
-int Engine::build_graph(int nact) {
+int Engine::build_graph(int nact, hipGraphExec_t* exec) {
     rec_nact = nact;
-    return graphs.build(nact, stream, [&]() { return record_step(); });
+    return graphs.get(nact, stream, [&]() { return record_step(); }, exec);
 }
 
 // ------------------------------------------------------------- driving
@@ -649,12 +690,16 @@ int Engine::decode(int n, int use_graph) {
                  "decode: tp_world > 1 needs an RCCL id at create or the one-shot exchange (xchg_open + set_exchange)");
     LLMI_REQUIRE(n >= 0 && host_next_pos + n <= c.max_seq, "decode: would run past max_seq");
     if (decode_mode == 1 && n > 0) LLMI_TRY(prepare_ring());
-    if (use_graph && n > 0)  // every graph this run replays, captured before the first launch
-        for (int k = nact_of(host_next_pos); k <= nact_of(host_next_pos + n - 1); ++k) LLMI_TRY(build_graph(k));
+    const int k0 = nact_of(host_next_pos);
+    std::vector<hipGraphExec_t> steps;  // every graph this run replays, captured before the first launch
+    if (use_graph && n > 0) {
+        steps.resize(nact_of(host_next_pos + n - 1) - k0 + 1);
+        for (size_t j = 0; j < steps.size(); ++j) LLMI_TRY(build_graph(k0 + (int)j, &steps[j]));
+    }
     for (int i = 0; i < n; ++i) {
         const int k = nact_of(host_next_pos + i);
         if (use_graph) {
-            LLMI_HIP(hipGraphLaunch(graphs.x[k], stream));
+            LLMI_HIP(hipGraphLaunch(steps[k - k0], stream));
         } else {
             rec_nact = k;
             LLMI_TRY(record_step());
@@ -673,11 +718,7 @@ int Engine::tokens_out(int32_t* out, int n, int* n_valid) {
     LLMI_HIP(hipStreamSynchronize(stream));
     DecodeState h;
     LLMI_HIP(hipMemcpy(&h, st, sizeof(h), hipMemcpyDeviceToHost));
-    LLMI_REQUIRE(h.error == 0, "decode: device error flag " + std::to_string(h.error) +
-                                   " (1: token id out of range, 2: position overflow, 4: attention split count != device position, "
-                                   "8: a tensor-parallel peer never arrived (one-shot exchange timeout), "
-                                   "16: a prefill gate_up lo partial never arrived, 32: a ring-layer hand-off timed out, "
-                                   "64: a fused q/k/v + attention wait timed out)");
+    LLMI_REQUIRE(h.error == 0, "decode: device error flag " + error_flag_text(h.error));
     const int m = n < valid ? n : valid;
     if (m > 0) LLMI_HIP(hipMemcpy(out, tokens, (size_t)m * 4, hipMemcpyDeviceToHost));
     if (n_valid) *n_valid = valid;

@@ -430,8 +430,8 @@ int llmi_engine_debug_timeline(llmi_engine* e, void* dev_buf, size_t bytes, int 
     LLMI_REQUIRE(e, "debug_timeline: null engine");
     Engine& g = e->e;
     LLMI_HIP(hipSetDevice(g.device));
-    LLMI_HIP(hipStreamSynchronize(g.stream));
-    g.graphs.clear();  // the captured steps carry the stamp pointers: re-capture
+    LLMI_HIP(hipStreamSynchronize(g.stream));  // (also an eager step: the caller may free its last buffer next)
+    LLMI_TRY(g.invalidate());  // the captured steps carry the stamp pointers: re-capture
     if (!dev_buf) {
         g.dbg_stamps = nullptr;
         g.dbg_stride = g.dbg_slots = 0;
@@ -594,37 +594,32 @@ int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_p
     LLMI_REQUIRE(b && p, "batch_set_sampling_params: null batch or params");
     LLMI_TRY(b->b.slot_ok(seq));
     LLMI_HIP(hipSetDevice(b->b.r[0]->device));
-    LLMI_TRY(b->b.r[seq]->set_sampling_params(*p));
-    return b->b.drop_graphs();  // the captured steps change
+    return b->b.r[seq]->set_sampling_params(*p);
 }
 
-// The slot's own engine setters; the batch's captured steps are dropped wherever the engine
-// form clears its graphs (always for the rules, for a mask only when it turns the rules on or off).
+// The slot's own engine setters: wherever one drops the engine's captured steps it drops the
+// batch's (Engine::invalidate).
 int llmi_batch_set_logit_rules(llmi_batch* b, int seq, const int32_t* bias_ids, const float* bias_values, int n_bias,
                                float presence_penalty, float frequency_penalty, int count_prompt) {
     LLMI_REQUIRE(b, "batch_set_logit_rules: null batch");
     LLMI_TRY(b->b.slot_ok(seq));
     LLMI_HIP(hipSetDevice(b->b.r[0]->device));
-    LLMI_TRY(b->b.r[seq]->set_logit_rules(bias_ids, bias_values, n_bias, presence_penalty, frequency_penalty,
-                                          count_prompt));
-    return b->b.drop_graphs();
+    return b->b.r[seq]->set_logit_rules(bias_ids, bias_values, n_bias, presence_penalty, frequency_penalty,
+                                        count_prompt);
 }
 
 int llmi_batch_set_allowed(llmi_batch* b, int seq, const int32_t* ids, int n) {
     LLMI_REQUIRE(b, "batch_set_allowed: null batch");
     LLMI_TRY(b->b.slot_ok(seq));
     LLMI_HIP(hipSetDevice(b->b.r[0]->device));
-    const bool was_on = b->b.r[seq]->rules_on();
-    LLMI_TRY(b->b.r[seq]->set_allowed(ids, n));
-    return b->b.r[seq]->rules_on() != was_on ? b->b.drop_graphs() : LLMI_OK;
+    return b->b.r[seq]->set_allowed(ids, n);
 }
 
 int llmi_batch_clear_logit_rules(llmi_batch* b, int seq) {
     LLMI_REQUIRE(b, "batch_clear_logit_rules: null batch");
     LLMI_TRY(b->b.slot_ok(seq));
     LLMI_HIP(hipSetDevice(b->b.r[0]->device));
-    LLMI_TRY(b->b.r[seq]->clear_logit_rules());
-    return b->b.drop_graphs();
+    return b->b.r[seq]->clear_logit_rules();
 }
 
 int llmi_batch_processed_logits(llmi_batch* b, int seq, float* out, int n) {
@@ -638,7 +633,7 @@ int llmi_batch_set_logprobs(llmi_batch* b, int seq, int n_top) {
     LLMI_REQUIRE(b, "batch_set_logprobs: null batch");
     LLMI_TRY(b->b.slot_ok(seq));
     LLMI_HIP(hipSetDevice(b->b.r[0]->device));
-    return b->b.r[seq]->set_logprobs(n_top);  // (the graph key carries every slot's setting)
+    return b->b.r[seq]->set_logprobs(n_top);
 }
 
 int llmi_batch_logprobs(llmi_batch* b, int seq, float* tok_lp, int32_t* top_ids, float* top_lp, int n, int* n_valid,

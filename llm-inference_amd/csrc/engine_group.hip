@@ -4,7 +4,7 @@
 namespace llmi {
 
 Group::~Group() {
-    graphs.clear();
+    (void)graphs.drop(stream);  // before the ranks whose launches they hold, and the stream
     r.clear();
     if (ptrs) (void)hipFree(ptrs);
     if (stream) (void)hipStreamDestroy(stream);
@@ -12,10 +12,7 @@ Group::~Group() {
 
 int Group::init(const llmi_config& cfg, int world, int dev) {
     LLMI_REQUIRE(world >= 1 && world <= 64, "group: world must be 1..64");
-    if (cfg.weight_dtype == LLMI_I4) {
-        set_last_error("[llmi][ERROR] group: int4 weights run on a single-rank engine only (no tensor parallel)");
-        return LLMI_EUNSUPPORTED;
-    }
+    LLMI_TRY(Engine::refuse("group", kModeTp, Engine::config_modes(cfg)));
     LLMI_HIP(hipSetDevice(dev));
     LLMI_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
     for (int i = 0; i < world; ++i) {
@@ -48,8 +45,7 @@ int Group::set_exchange(int mode) {
         }
         for (auto& e : r) LLMI_TRY(e->set_peers(inboxes));  // same device: the inboxes themselves
     }
-    LLMI_HIP(hipStreamSynchronize(stream));
-    graphs.clear();
+    LLMI_TRY(graphs.drop(stream));  // the captured steps change
     xchg_mode = mode;
     for (auto& e : r) e->tail_mode = mode == 2 ? 1 : 0;
     return LLMI_OK;
@@ -86,13 +82,17 @@ int Group::decode(int n, int use_graph) {
     Engine& e0 = *r[0];
     LLMI_REQUIRE(e0.prompt_len > 0, "group decode: set_prompt first");
     LLMI_REQUIRE(n >= 0 && e0.host_next_pos + n <= e0.c.max_seq, "group decode: would run past max_seq");
-    if (use_graph && n > 0)
-        for (int k = Engine::nact_of(e0.host_next_pos); k <= Engine::nact_of(e0.host_next_pos + n - 1); ++k)
-            LLMI_TRY(graphs.build(k, stream, [&]() { return record_step(k); }));
+    const int k0 = Engine::nact_of(e0.host_next_pos);
+    std::vector<hipGraphExec_t> steps;  // every graph this run replays, captured before the first launch
+    if (use_graph && n > 0) {
+        steps.resize(Engine::nact_of(e0.host_next_pos + n - 1) - k0 + 1);
+        for (int k = k0; k < k0 + (int)steps.size(); ++k)
+            LLMI_TRY(graphs.get(k, stream, [&]() { return record_step(k); }, &steps[k - k0]));
+    }
     for (int i = 0; i < n; ++i) {
         const int k = Engine::nact_of(e0.host_next_pos + i);
         if (use_graph)
-            LLMI_HIP(hipGraphLaunch(graphs.x[k], stream));
+            LLMI_HIP(hipGraphLaunch(steps[k - k0], stream));
         else
             LLMI_TRY(record_step(k));
     }

@@ -163,40 +163,12 @@ __global__ __launch_bounds__(kSpecT) void spec_commit_kernel(SpecLanes L, int np
     }
 }
 
-int spec_unsupported(const char* what) {
-    set_last_error(std::string("[llmi][ERROR] set_speculation: ") + what);
-    return LLMI_EUNSUPPORTED;
-}
-
 }  // namespace
-
-void Engine::clear_spec_graphs() {
-    for (auto& kv : spec_graphs) {
-        if (kv.second.second) (void)hipGraphExecDestroy(kv.second.second);
-        if (kv.second.first) (void)hipGraphDestroy(kv.second.first);
-    }
-    spec_graphs.clear();
-}
-
-// the reason a speculating engine cannot take this configuration, or null
-const char* Engine::spec_refusal() const {
-    if (c.tp_world != 1 || grouped) return "tensor-parallel ranks and group ranks are not built (tp_world must be 1)";
-    if (wdt == LLMI_I4) return "int4 weights are not built into the multi-row GEMV";
-    if (c.kv_dtype == LLMI_I8) return "an int8 KV cache is not built into the multi-row attention";
-    if (decode_mode == 1) return "the ring decode mode has no verify step (set_decode_mode 0)";
-    if (sample_k > 0 || nuc_on) return "a sampler is active (speculative sampling is not built; greedy only)";
-    if (lp_top >= 0) return "logprobs are on (the verify step records none)";
-    if (rules_on()) return "logit rules are on (the verify step applies none; clear_logit_rules first)";
-    return nullptr;
-}
 
 int Engine::set_speculation(int max_draft) {
     LLMI_REQUIRE(max_draft >= 0 && max_draft <= kAttnRowsMax - 1, "set_speculation: max_draft must be in [0, 7]");
-    if (max_draft > 0) {
-        if (const char* why = spec_refusal()) return spec_unsupported(why);
-    }
-    LLMI_HIP(hipStreamSynchronize(stream));  // a replay may still be in flight
-    clear_spec_graphs();
+    if (max_draft > 0) LLMI_TRY(refuse("set_speculation", kModeSpec));
+    LLMI_TRY(spec_graphs.drop(stream));  // (the token steps stay: no lane is part of them)
     if (max_draft > 0 && !spec_draft) {
         LLMI_HIP(hipMalloc(&spec_draft, (kAttnRowsMax + 4) * sizeof(int32_t)));
         LLMI_HIP(hipMemset(spec_draft, 0, (kAttnRowsMax + 4) * sizeof(int32_t)));
@@ -211,26 +183,13 @@ int Engine::set_speculation(int max_draft) {
     return LLMI_OK;
 }
 
-// one multi-row GEMV from the lanes' own single-row arguments (as Batch::rows)
-template <typename F>
-int Engine::spec_rows(int m, F&& args_of) {
-    GemvRowsArgs p;
-    p.m = m;
-    for (int i = 0; i < m; ++i) {
-        const GemvArgs a = args_of(i == 0 ? *this : *lanes[i - 1]);
-        if (i == 0) p.a = a;
-        GemvRow& w = p.row[i];
-        w.x = a.x; w.x_fixed = a.x_fixed; w.x_out = a.x_out; w.y = a.y; w.resid = a.resid;
-        w.yacc = a.yacc; w.yacc_base = a.yacc_base; w.yacc_copy = a.yacc_copy; w.partials = a.partials;
-        w.seed_src = a.seed_src; w.seed_dst = a.seed_dst;
-    }
-    p.a.stamps = nullptr;
-    return gemv_rows_launch(p, stream);
-}
-
 // one verify step of m = 2..8 rows; rec_nact = the split count of the last row's position
 int Engine::record_verify(int m) {
     auto lane = [&](int i) -> Engine& { return i == 0 ? *this : *lanes[i - 1]; };
+    std::vector<Engine*> es;
+    for (int i = 0; i < m; ++i) es.push_back(&lane(i));
+    // one multi-row GEMV from the lanes' own single-row arguments (no debug stamps)
+    auto spec_rows = [&](auto&& args_of) { return gemv_rows_of(es, stream, args_of, false); };
     SpecLanes L;
     L.m = m;
     for (int i = 0; i < kAttnRowsMax; ++i) {
@@ -247,7 +206,7 @@ int Engine::record_verify(int m) {
                            spec_draft, (const float*)embed, c.hidden, c.max_seq);
     LLMI_HIP(hipGetLastError());
     for (int l = 0; l < c.layers; ++l) {
-        LLMI_TRY(spec_rows(m, [&](Engine& e) { return e.qkv_args(l); }));
+        LLMI_TRY(spec_rows([&](Engine& e) { return e.qkv_args(l); }));
         AttnRowsArgs at;
         OprojRowsArgs o;
         at.m = o.m = m;
@@ -269,10 +228,10 @@ int Engine::record_verify(int m) {
         o.a.stamps = nullptr;
         LLMI_TRY(attn_rows_launch(at, stream));
         LLMI_TRY(oproj_rows_launch(o, stream));
-        LLMI_TRY(spec_rows(m, [&](Engine& e) { return e.gu_args(l); }));
-        LLMI_TRY(spec_rows(m, [&](Engine& e) { return e.down_args(l); }));
+        LLMI_TRY(spec_rows([&](Engine& e) { return e.gu_args(l); }));
+        LLMI_TRY(spec_rows([&](Engine& e) { return e.down_args(l); }));
     }
-    LLMI_TRY(spec_rows(m, [&](Engine& e) { return e.lm_args(); }));
+    LLMI_TRY(spec_rows([&](Engine& e) { return e.lm_args(); }));
     hipLaunchKernelGGL(spec_commit_kernel, dim3(1), dim3(kSpecT), 0, stream, L, lm_grid, tokens, spec_draft, c.hidden,
                        vl, c.max_seq, out);
     LLMI_HIP(hipGetLastError());
@@ -288,9 +247,7 @@ int Engine::verify(const int32_t* draft, int n_draft, int use_graph, int* n_acce
     LLMI_REQUIRE(host_next_pos + n_draft + 1 <= c.max_seq, "verify: would run past max_seq");
     for (int i = 0; i < n_draft; ++i)
         LLMI_REQUIRE(draft[i] >= 0 && draft[i] < c.vocab, "verify: draft id out of range");
-    if (n_draft > 0) {
-        if (const char* why = spec_refusal()) return spec_unsupported(why);
-    }
+    if (n_draft > 0) LLMI_TRY(refuse("set_speculation", kModeSpec));
     const int m = n_draft + 1;
     int out[3] = {0, 0, 0};
     if (m == 1) {  // the engine's own single-row step
@@ -305,19 +262,9 @@ int Engine::verify(const int32_t* draft, int n_draft, int use_graph, int* n_acce
         LLMI_HIP(hipMemcpyAsync(spec_draft, draft, (size_t)n_draft * 4, hipMemcpyHostToDevice, stream));
         rec_nact = nact_of(host_next_pos + n_draft);
         if (use_graph) {
-            const std::pair<int, int> key(m, rec_nact);
-            auto it = spec_graphs.find(key);
-            if (it == spec_graphs.end()) {
-                if (spec_graphs.size() >= kMaxSpecGraphs) {
-                    LLMI_HIP(hipStreamSynchronize(stream));
-                    clear_spec_graphs();
-                }
-                hipGraph_t h = nullptr;
-                hipGraphExec_t x = nullptr;
-                LLMI_TRY(capture(stream, [&]() { return record_verify(m); }, &h, &x));
-                it = spec_graphs.emplace(key, std::make_pair(h, x)).first;
-            }
-            LLMI_HIP(hipGraphLaunch(it->second.second, stream));
+            hipGraphExec_t step = nullptr;
+            LLMI_TRY(spec_graphs.get({m, rec_nact}, stream, [&]() { return record_verify(m); }, &step));
+            LLMI_HIP(hipGraphLaunch(step, stream));
         } else {
             LLMI_TRY(record_verify(m));
         }
@@ -326,9 +273,7 @@ int Engine::verify(const int32_t* draft, int n_draft, int use_graph, int* n_acce
         LLMI_REQUIRE(out[0] >= 0 && out[0] <= n_draft, "verify: the device reported an impossible accepted count");
         host_next_pos += out[0] + 1;
     }
-    LLMI_REQUIRE(out[2] == 0, "verify: device error flag " + std::to_string(out[2]) +
-                                  " (1: token id out of range, 2: position overflow, 4: attention split count != "
-                                  "device position)");
+    LLMI_REQUIRE(out[2] == 0, "verify: device error flag " + error_flag_text(out[2]));
     *n_accepted = out[0];
     if (next_token) *next_token = out[1];
     return LLMI_OK;
@@ -395,7 +340,7 @@ int Engine::read_ids(int from, int n, int32_t* out) {
     LLMI_HIP(hipStreamSynchronize(stream));
     int err = 0;
     LLMI_HIP(hipMemcpy(&err, &st->error, sizeof(int), hipMemcpyDeviceToHost));
-    LLMI_REQUIRE(err == 0, "generate_draft: the draft's device error flag " + std::to_string(err));
+    LLMI_REQUIRE(err == 0, "generate_draft: the draft's device error flag " + error_flag_text(err));
     LLMI_REQUIRE(from >= 0 && n >= 0 && from + n <= c.max_seq + 1, "generate_draft: ids out of range");
     if (n > 0) LLMI_HIP(hipMemcpy(out, tokens + from, (size_t)n * 4, hipMemcpyDeviceToHost));
     return LLMI_OK;
@@ -430,10 +375,7 @@ int Engine::generate_draft(Engine& d, int n_steps, int max_draft, int draft_pref
     LLMI_REQUIRE(d.c.vocab == c.vocab, "generate_draft: the draft's vocab differs from the target's");
     LLMI_REQUIRE(d.device == device, "generate_draft: the draft is on another device");
     LLMI_REQUIRE(d.c.max_seq >= c.max_seq, "generate_draft: the draft's max_seq is smaller than the target's");
-    if (const char* why = spec_refusal()) {
-        set_last_error(std::string("[llmi][ERROR] generate_draft: the target: ") + why);
-        return LLMI_EUNSUPPORTED;
-    }
+    LLMI_TRY(refuse("generate_draft: the target", kModeSpec));
     LLMI_REQUIRE(max_draft >= 0 && max_draft <= spec_max, "generate_draft: max_draft must be in [0, set_speculation's]");
     LLMI_REQUIRE(prompt_len > 0 && host_next_pos >= prompt_len, "generate_draft: the target's prompt is not consumed yet");
     LLMI_REQUIRE(host_next_pos + n_steps <= c.max_seq, "generate_draft: would run past max_seq");

@@ -11,8 +11,8 @@ Engine::~Engine() {  // teardown errors are not actionable; ignore them explicit
     if (samp_vals) (void)hipFree(samp_vals);
     if (lr_bias) (void)hipFree(lr_bias);  // (lr_allowed is part of scratch)
     if (lr_out) (void)hipFree(lr_out);
-    graphs.clear();
-    clear_spec_graphs();
+    (void)graphs.drop(stream);  // the captured steps before the buffers their launches name
+    (void)spec_graphs.drop(stream);
     lanes.clear();  // the verify lanes before what they borrow
     if (spec_draft) (void)hipFree(spec_draft);
     if (comm) (void)ncclCommDestroy(comm);

@@ -124,6 +124,14 @@ struct GemvRowsArgs {
     int m = 0;
     GemvRow row[kGemvRowsMax];
 };
+// append the activation row of the single-row arguments r (the first row's also become p.a)
+inline void gemv_rows_add(GemvRowsArgs& p, const GemvArgs& r) {
+    if (p.m == 0) p.a = r;
+    GemvRow& w = p.row[p.m++];
+    w.x = r.x; w.x_fixed = r.x_fixed; w.x_out = r.x_out; w.y = r.y; w.resid = r.resid;
+    w.yacc = r.yacc; w.yacc_base = r.yacc_base; w.yacc_copy = r.yacc_copy; w.partials = r.partials;
+    w.seed_src = r.seed_src; w.seed_dst = r.seed_dst;
+}
 // the single-row arguments of activation row i (what the row's result is defined by)
 GemvArgs gemv_rows_single(const GemvRowsArgs& p, int i);
 // LLMI_EUNSUPPORTED: kpar > 1, granule rows, a fused exchange tail, stamps, or an input form the
@@ -492,12 +500,7 @@ struct DecodeState {
     int cur_pos;      // position of the forward in flight
     int prompt_len;
     int vocab;
-    int error;        // sticky error flags (1: token id out of range, 2: position overflow,
-                      // 4: host-sized attention grid != device position's split count,
-                      // 8: a tensor-parallel peer never arrived (one-shot exchange timeout, xchg.hip),
-                      // 16: a prefill gate_up lo partial never arrived, gemm3_silu_bal_kernel,
-                      // 32: a ring-layer hand-off or ring-slot wait timed out, ring.hip,
-                      // 64: a fused q/k/v + attention workgroup's wait for its rows timed out)
+    int error;        // sticky error flags, bits 1 .. 64: error_flag_text (engine.hip) has the legend
     unsigned epoch;   // forwards stepped since the engine was created (step_start; never reset
                       // by set_prompt): tags the fused q/k/v launch's granules
     int pad[2];
