@@ -458,6 +458,25 @@ int llmi_attn_decode_q8(const float* qkv, void* k_cache, void* v_cache, int cach
                         float rope_base, float* out, void* workspace, llmi_stream_t stream, void* k_scale,
                         void* v_scale);
 
+/* Copy the first n_rows cached rows of a whole cache to other caches (no reference counterpart;
+ * what llmi_batch_fork does to the rows): rows [0, n_rows) of every (layer, kv head) of src_k and
+ * src_v [layers, kv_heads, max_seq, 128] of cache_dtype LLMI_F32, LLMI_F16 or LLMI_I8 go to
+ * dst_k[i] / dst_v[i] of the same shape, i < n_dst, raw bytes. One launch (kv_copy_rows_kernel):
+ * every source byte is read once and stored n_dst times. With LLMI_I8 the fp16 scales
+ * [layers, kv_heads, max_seq] (src_k_scale / src_v_scale -> dst_k_scale[i] / dst_v_scale[i]) are
+ * copied as well; with the other dtypes the scale arguments are ignored and may be null. dst_*
+ * are HOST arrays of n_dst device pointers, read before the call returns. Rows at or after n_rows
+ * and their scales are not written in any destination; the source is only read. Any max_seq is
+ * taken. Stream-ordered, no synchronisation, capturable.
+ *   LLMI_EINVAL, with nothing launched: n_dst outside 1..7, n_rows outside [0, max_seq],
+ * head_dim != 128, another cache dtype, a null or not 16-byte aligned buffer, a destination that
+ * is the source or appears twice, LLMI_I8 without scales. n_rows == 0 succeeds and launches
+ * nothing. */
+int llmi_kv_copy_rows(const void* src_k, const void* src_v, const void* src_k_scale, const void* src_v_scale,
+                      void* const* dst_k, void* const* dst_v, void* const* dst_k_scale, void* const* dst_v_scale,
+                      int n_dst, int cache_dtype, int layers, int kv_heads, int max_seq, int head_dim, int n_rows,
+                      llmi_stream_t stream);
+
 /* launchTopKforBeamSearch + launchSampling (src/kernels/topK.h:51-56,
  * sampling.h:12-18) as wired by Llama<T> (K = beamwidth = 1, llama.cpp:59):
  * greedy argmax over logits[n]; ties -> lowest index. out_id: device int32. */
@@ -1178,6 +1197,38 @@ int llmi_batch_reset(llmi_batch* b, int seq);
  * the edited engine would alone, the other slots as if nothing happened. LLMI_EINVAL for a seq
  * out of range, an idle slot, and llmi_engine_edit's own. */
 int llmi_batch_edit(llmi_batch* b, int seq, int keep, const int32_t* ids, int n);
+/* Fork a slot (no reference counterpart): copy slot src's sequence -- cache rows, ids and decode
+ * state -- into the n_dst (1..7) slots dst[], on the device and in stream order, so that n
+ * continuations of one prompt cost one prompt pass. With P the source's next position
+ * (keep = -1 means P), two forms:
+ *   Cut (n >= 1, 0 <= keep <= P, keep + n <= max_seq): every destination becomes what the source
+ * would be after llmi_batch_edit(b, src, keep, ids, n) -- rows [0, keep) of every layer's K and V
+ * (and their KV8 scales) and ids [0, keep) are the source's bytes, positions keep .. keep + n - 1
+ * take ids as a prompt would, the next position is keep and the prompt length keep + n, the
+ * pending token is forgotten. It goes on bitwise as the edited source would. keep == 0 copies no
+ * row: llmi_batch_set_prompt(ids) without its synchronise.
+ *   Continue (n == 0, keep == P): every destination is the source as it stands, the pending token
+ * included: also copied are the prompt and its length, the argmax partials, the raw logits row,
+ * and the processed row where source and destination both have logit rules on. The next step of
+ * a destination picks the token the source's next step picks; with a sampler, later tokens
+ * follow the destination's own seed.
+ *   Both: the source is only read and goes on as if nothing happened. A destination keeps its
+ * own sampler, seed, logit rules, allowed set and logprob setting; whatever sequence it held is
+ * gone, an idle one becomes active. Its device error word becomes the source's (a fork of a
+ * faulted sequence is faulted); its forward counter is left alone. Logprob records are copied
+ * where source and destination both have logprobs on with the same n_top -- records [0, keep) in
+ * the cut form (record keep stays not computed, as after llmi_engine_edit), [0, P] in the
+ * continue form -- and every other record of the destination becomes "not computed"; with any
+ * other combination of settings all of them do. The destination's scored-prefill slab is
+ * forgotten. The captured step graphs stay valid: no buffer moves.
+ *   Two stream-ordered launches (kv_copy_rows_kernel, none for keep == 0; seq_fork_kernel). For
+ * n <= 8 the ids travel in the launch arguments and the call neither copies nor synchronises; a
+ * longer list is copied first and the call synchronises (as llmi_engine_edit).
+ *   LLMI_EINVAL, with nothing changed: src out of range or idle; n_dst outside 1..7; a
+ * destination out of range, equal to src or listed twice; keep or n outside the ranges above; an
+ * id outside [0, vocab); n == 0 with keep != P (a cut needs a forced id: the pending token is
+ * forgotten). */
+int llmi_batch_fork(llmi_batch* b, int src, const int* dst, int n_dst, int keep, const int32_t* ids, int n);
 /* llmi_engine_set_sampling_params for one slot: step = seed + the sampled token's position,
  * row 0, as in the engine. */
 int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_params* p);

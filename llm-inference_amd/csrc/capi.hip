@@ -567,6 +567,33 @@ int llmi_attn_decode_q8(const float* qkv, void* k_cache, void* v_cache, int cach
     return attn_decode_launch(a, STREAM(stream));
 }
 
+int llmi_kv_copy_rows(const void* src_k, const void* src_v, const void* src_k_scale, const void* src_v_scale,
+                      void* const* dst_k, void* const* dst_v, void* const* dst_k_scale, void* const* dst_v_scale,
+                      int n_dst, int cache_dtype, int layers, int kv_heads, int max_seq, int head_dim, int n_rows,
+                      llmi_stream_t stream) {
+    LLMI_REQUIRE(n_dst >= 1 && n_dst <= kKvCopyMaxDst, "kv_copy_rows: n_dst must be 1..7");
+    LLMI_REQUIRE(dst_k && dst_v, "kv_copy_rows: null destination arrays");
+    KvCopyArgs a;
+    a.src_k = src_k;
+    a.src_v = src_v;
+    a.src_k_scale = src_k_scale;
+    a.src_v_scale = src_v_scale;
+    for (int d = 0; d < n_dst; ++d) {
+        a.dst_k[d] = dst_k[d];
+        a.dst_v[d] = dst_v[d];
+        a.dst_k_scale[d] = dst_k_scale ? dst_k_scale[d] : nullptr;
+        a.dst_v_scale[d] = dst_v_scale ? dst_v_scale[d] : nullptr;
+    }
+    a.n_dst = n_dst;
+    a.cache_dtype = cache_dtype;
+    a.layers = layers;
+    a.kv_heads = kv_heads;
+    a.max_seq = max_seq;
+    a.head_dim = head_dim;
+    a.n_rows = n_rows;
+    return kv_copy_rows_launch(a, STREAM(stream));
+}
+
 int llmi_topk(const void* logits, int dtype, int rows, int vocab, int k, int32_t* topk_ids, void* topk_vals,
               llmi_stream_t stream) {
     return topk_launch(logits, dtype, rows, vocab, k, topk_ids, topk_vals, STREAM(stream));

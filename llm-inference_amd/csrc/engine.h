@@ -40,12 +40,15 @@
 // own caches and those of the owner whose steps hold this engine's launches (a slot's batch, a
 // verify lane's engine). A Group drops its own cache in Group::set_exchange. Replacing the
 // contents of an allowed-token mask that is already present is a stream-ordered copy into a
-// fixed buffer and invalidates nothing.
+// fixed buffer and invalidates nothing. Neither does a fork (Engine::fork_into, Batch::fork): a
+// batch step's key is (slot, split count) and its launches hold the slot's own buffers, none of
+// which move; the fork only writes their contents, in stream order (as set_prompt and edit do).
 //
 // One struct Engine, defined over several units: engine_weights.hip (setup and the
 // loaders), engine.hip (the token step, the TP exchange, the ring layer, the setters),
 // engine_prefill.hip, engine_spec.hip (the verify step, the lookup and draft-engine loops),
-// engine_edit.hip (rewind / extend a sequence), engine_group.hip / engine_batch.hip (Group,
+// engine_edit.hip (rewind / extend a sequence), engine_fork.hip (copy a sequence into other
+// slots; the cache rows through kv_fork.hip), engine_group.hip / engine_batch.hip (Group,
 // Batch), engine_capi.hip (the C ABI) and engine_time.hip (llmi_engine_time_kernel).
 #pragma once
 #include <rccl/rccl.h>
@@ -510,6 +513,10 @@ struct Engine {
 
     // ---- engine_edit.hip: keep a prefix of the sequence, force the ids that follow
     int edit(int keep, const int32_t* ids, int n);
+
+    // ---- engine_fork.hip: copy this sequence into other engines on this stream (a batch's slots),
+    // cut at `keep` with forced ids as edit would (n >= 1), or as it stands (n == 0, keep == position)
+    int fork_into(const std::vector<Engine*>& dst, int keep, const int32_t* ids, int n);
 };
 // prompt-lookup drafting on the host (llmi_lookup_draft)
 int lookup_draft(const int32_t* ids, int n, int ngram_max, int ngram_min, int max_draft, int32_t* out, int* n_out);
@@ -567,6 +574,7 @@ struct Batch {
     int record_step(const std::vector<int>& act);
     int decode(int n, int use_graph);
     int prefill(int seq, int n, int split, bool scored);
+    int fork(int src, const int* dst, int n_dst, int keep, const int32_t* ids, int n);  // engine_fork.hip
 };
 
 }  // namespace llmi

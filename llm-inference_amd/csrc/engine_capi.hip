@@ -585,6 +585,12 @@ int llmi_batch_edit(llmi_batch* b, int seq, int keep, const int32_t* ids, int n)
     return b->b.r[seq]->edit(keep, ids, n);  // (an idle slot has no prompt: LLMI_EINVAL)
 }
 
+int llmi_batch_fork(llmi_batch* b, int src, const int* dst, int n_dst, int keep, const int32_t* ids, int n) {
+    LLMI_REQUIRE(b, "batch_fork: null batch");
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    return b->b.fork(src, dst, n_dst, keep, ids, n);
+}
+
 int llmi_batch_reset(llmi_batch* b, int seq) {
     LLMI_REQUIRE(b, "null batch");
     return b->b.reset(seq);

@@ -605,6 +605,23 @@ int engine_logit_rules_check(int vocab, int max_seq, float presence, float frequ
 int engine_logit_rules_launch(const struct DecodeState* st, const float* logits, int vocab, const float* bias,
                               const uint32_t* allowed, const int32_t* tokens, int count_prompt, float presence,
                               float frequency, float* out, unsigned long long* partials, int np, hipStream_t s);
+// rows [0, n_rows) of every (layer, kv head) of a K and a V cache [layers, kv_heads, max_seq, 128]
+// (and, int8, of their fp16 scales [layers, kv_heads, max_seq]) from one source to n_dst
+// destinations in one launch (kv_fork.hip; the contract: llmi_kv_copy_rows in include/llmi.h)
+constexpr int kKvCopyMaxDst = 7;
+struct KvCopyArgs {
+    const void *src_k = nullptr, *src_v = nullptr;
+    const void *src_k_scale = nullptr, *src_v_scale = nullptr;
+    void* dst_k[kKvCopyMaxDst] = {};
+    void* dst_v[kKvCopyMaxDst] = {};
+    void* dst_k_scale[kKvCopyMaxDst] = {};
+    void* dst_v_scale[kKvCopyMaxDst] = {};
+    int n_dst = 0;
+    int cache_dtype = LLMI_F16;
+    int layers = 0, kv_heads = 0, max_seq = 0, head_dim = 128, n_rows = 0;
+    int n_cu = 0;  // the device's CU count where the caller knows it (0: asked for)
+};
+int kv_copy_rows_launch(const KvCopyArgs& a, hipStream_t s);
 int repeat_kv_launch(const void* k_cache, const void* v_cache, int dtype, int layer, const int* ctx_len, int batch,
                      int kv_heads, int max_seq, int heads, int max_k_len, int d, void* k_dst, void* v_dst,
                      hipStream_t s);

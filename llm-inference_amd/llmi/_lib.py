@@ -116,6 +116,7 @@ _SIGS = {
     "llmi_attn_workspace_bytes": (_SZ, [_I, _I, _I]),
     "llmi_attn_decode": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "llmi_attn_decode_q8": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
+    "llmi_kv_copy_rows": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "llmi_argmax": (_I, [_P, _I, _P, _P]),
     "llmi_topk": (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     "llmi_sampling": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
@@ -241,6 +242,7 @@ _SIGS = {
     "llmi_batch_load_bin_quantized": (_I, [_P, C.c_char_p]),
     "llmi_batch_set_prompt": (_I, [_P, _I, _P, _I]),
     "llmi_batch_reset": (_I, [_P, _I]),
+    "llmi_batch_fork": (_I, [_P, _I, _P, _I, _I, _P, _I]),
     "llmi_batch_set_sampling_params": (_I, [_P, _I, _P]),
     "llmi_batch_set_logprobs": (_I, [_P, _I, _I]),
     "llmi_batch_logprobs": (_I, [_P, _I, _P, _P, _P, _I, C.POINTER(_I), C.POINTER(_I)]),

@@ -588,6 +588,63 @@ class Batch:
         if len(ids):
             self._plen[int(seq)], self._pos[int(seq)] = int(keep) + len(ids), int(keep)
 
+    def fork(self, src: int, dst, keep: Optional[int] = None, ids=()):
+        """Copy slot src's sequence into the slot(s) dst (an int or up to 7 ints) on the device, in
+        stream order (llmi_batch_fork): the cache rows, the ids and the decode state. With ids,
+        every destination becomes what src would be after edit(src, keep, ids) -- the first keep
+        positions kept (None: all consumed ones), the pending token forgotten, ids forced next.
+        Without ids (keep None or src's position) it becomes src as it stands, pending token
+        included. A destination keeps its own sampler, seed, logit rules and logprob setting;
+        src is left as it is."""
+        src = int(src)
+        dst = [int(dst)] if isinstance(dst, (int, np.integer)) else [int(d) for d in dst]
+        ids = np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        to = (C.c_int * max(len(dst), 1))(*dst)
+        call("llmi_batch_fork", self._h, src, to, len(dst), -1 if keep is None else int(keep),
+             ids.ctypes.data if len(ids) else None, len(ids))
+        pos = self._pos[src] if keep is None else int(keep)
+        for d in dst:
+            self._plen[d] = pos + len(ids) if len(ids) else self._plen[src]
+            self._pos[d] = pos
+
+    def sample(self, prompt, n: int, n_new: int, seeds=None, prefill: bool = True, use_graph: bool = True,
+               **sampling_params):
+        """n <= n_seq continuations of n_new tokens of one prompt for one prompt pass: every slot
+        is reset, slot i gets set_sampling_params(seed=seeds[i], **sampling_params) (seeds default
+        to the `seed` keyword + 0 .. n - 1), slot 0 consumes all but the last prompt row (one
+        prefill, or decode steps with prefill=False) and is forked into slots 1 .. n - 1, and the
+        n slots decode together from the last prompt position, so each continuation is bitwise
+        that of an Engine alone with that seed. Returns the n id arrays; where the n slots have
+        logprobs on, (ids, sums) with each continuation's summed token logprob (fp64 sum of the
+        fp32 records) for a best-of-n pick. The samplers stay set and the slots active."""
+        prompt = np.ascontiguousarray(prompt, dtype=np.int32).reshape(-1)
+        n, n_new, plen = int(n), int(n_new), len(prompt)
+        if not 1 <= n <= self.n_seq:
+            raise ValueError("sample: n must be in [1, n_seq]")
+        if plen < 1 or n_new < 1:
+            raise ValueError("sample: an empty prompt, or n_new < 1")
+        seed = int(sampling_params.pop("seed", 0))
+        seeds = [seed + i for i in range(n)] if seeds is None else [int(s) for s in seeds]
+        if len(seeds) != n:
+            raise ValueError("sample: one seed per continuation")
+        for i in range(self.n_seq):
+            self.reset(i)
+        for i in range(n):
+            self.set_sampling_params(i, seed=seeds[i], **sampling_params)
+        self.set_prompt(0, prompt)
+        if plen > 1 and prefill:
+            self.prefill(0, plen - 1)
+        elif plen > 1:
+            self.decode(plen - 1, use_graph)
+        if n > 1:
+            self.fork(0, range(1, n), keep=plen - 1, ids=prompt[-1:])
+        self.decode(n_new, use_graph)
+        out = [self.tokens(i, plen + n_new)[plen:] for i in range(n)]
+        if any(self._lp_top[i] < 0 for i in range(n)):
+            return out
+        sums = np.array([np.sum(self.logprobs(i, plen + n_new)[0][plen:], dtype=np.float64) for i in range(n)])
+        return out, sums
+
     def prefill(self, seq: int, n: Optional[int] = None, exact=True, score: bool = False):
         """Engine.prefill for one slot (llmi_batch_prefill): its next n prompt rows (None: the
         rest of its prompt) in one batched pass on the batch's stream; the other slots are

@@ -141,6 +141,44 @@ def attn_decode_q8(qkv, k_cache, v_cache, k_scale, v_scale, layer: int, pos: int
     return out
 
 
+def kv_copy_rows(src_k, src_v, dst_k, dst_v, n_rows: int, src_k_scale=None, src_v_scale=None, dst_k_scale=None,
+                 dst_v_scale=None):
+    """Rows [0, n_rows) of every (layer, kv head) of the caches src_k / src_v
+    [layers, kv_heads, max_seq, 128] (fp32, fp16 or int8) into each of the caches in the lists
+    dst_k / dst_v (1..7 of the same shape and dtype), in one launch (llmi_kv_copy_rows). int8
+    caches take their fp16 scales [layers, kv_heads, max_seq] along: src_*_scale and the lists
+    dst_*_scale. Nothing at or after row n_rows is written. The library checks the arguments
+    (LlmiError: LLMI_EINVAL); the tensors must be contiguous."""
+    dst_k, dst_v = list(dst_k), list(dst_v)
+    dst_ks = list(dst_k_scale) if dst_k_scale is not None else None
+    dst_vs = list(dst_v_scale) if dst_v_scale is not None else None
+    every = [src_k, src_v, src_k_scale, src_v_scale, *dst_k, *dst_v, *(dst_ks or []), *(dst_vs or [])]
+    _dev(*every)
+    n_dst = len(dst_k)
+    if len(dst_v) != n_dst or any(s is not None and len(s) != n_dst for s in (dst_ks, dst_vs)):
+        raise ValueError("kv_copy_rows: the destination lists must have one length")
+    if src_k.dim() != 4:
+        raise ValueError("kv_copy_rows: caches are [layers, kv_heads, max_seq, head_dim]")
+    for t in every:
+        if t is None:
+            continue
+        if not t.is_contiguous():
+            raise ValueError("kv_copy_rows: tensors must be contiguous")
+        scale = t.dim() == 3
+        if (t.dtype != (torch.float16 if scale else src_k.dtype)
+                or tuple(t.shape) != tuple(src_k.shape[:3] if scale else src_k.shape)):
+            raise ValueError("kv_copy_rows: every cache has the source's shape and dtype; scales are fp16 "
+                             "[layers, kv_heads, max_seq]")
+    layers, kv_heads, max_seq, head_dim = src_k.shape
+
+    def ptrs(ts):
+        return None if ts is None else (ctypes.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
+
+    call("llmi_kv_copy_rows", src_k.data_ptr(), src_v.data_ptr(), _p(src_k_scale), _p(src_v_scale), ptrs(dst_k),
+         ptrs(dst_v), ptrs(dst_ks), ptrs(dst_vs), n_dst, _dt(src_k), layers, kv_heads, max_seq, head_dim, int(n_rows),
+         _stream())
+
+
 def argmax(logits: torch.Tensor) -> torch.Tensor:
     _dev(logits)
     out = torch.empty(1, device=logits.device, dtype=torch.int32)
