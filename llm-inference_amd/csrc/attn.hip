@@ -94,21 +94,22 @@ __global__ __launch_bounds__(kThreads) void attn_merge_kernel(AttnArgs a, int ns
     if (tid < D) a.out[(size_t)h * D + tid] = (o_red[0][tid] + o_red[1][tid]) / L;
 }
 
-// Workgroup (h, row chunk of 16 * NPL rows): see oproj_body.
-template <typename WT, int NPL>
+// Workgroup (h, row chunk of 16 * NPL rows): see oproj_body. NB: the split bucket of a host-sized
+// launch (oproj_bucket(a.nact)), 0 for the position-derived form.
+template <typename WT, int NPL, int NB>
 __global__ __launch_bounds__(kThreads) void attn_oproj_kernel(OprojArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     WgStamp ts(a.stamps);
-    oproj_body<WT, NPL, PlainIO>(a, blockIdx.x, blockIdx.y, ns, smem);
+    oproj_body<WT, NPL, PlainIO, NB>(a, blockIdx.x, blockIdx.y, ns, smem);
     xchg_detail::xchg_tail(a.xt, a.xt_cnt, reinterpret_cast<int*>(smem));  // TP: push xacc from this launch
 }
 
 // two heads per workgroup (oproj_body2)
-template <typename WT, int NPL>
+template <typename WT, int NPL, int NB>
 __global__ __launch_bounds__(kThreads) void attn_oproj2_kernel(OprojArgs a, int ns) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     WgStamp ts(a.stamps);
-    oproj_body2<WT, NPL, PlainIO>(a, blockIdx.x, blockIdx.y, ns, smem);
+    oproj_body2<WT, NPL, PlainIO, false, NB>(a, blockIdx.x, blockIdx.y, ns, smem);
     xchg_detail::xchg_tail(a.xt, a.xt_cnt, reinterpret_cast<int*>(smem));  // TP: push xacc from this launch
 }
 
@@ -124,6 +125,28 @@ int oproj_npl(const OprojArgs& a) {
     return target >= 8 ? 8 : target >= 4 ? 4 : target >= 2 ? 2 : 1;
 }
 
+// the kernel instantiated on the launch's split bucket
+template <typename WT, int NPL>
+void oproj_launch_nb(const OprojArgs& a, int ns, dim3 grid, hipStream_t s) {
+    switch (oproj_bucket(a.nact)) {
+        case 0: hipLaunchKernelGGL((attn_oproj_kernel<WT, NPL, 0>), grid, dim3(kThreads), oproj_lds<NPL>(), s, a, ns); break;
+        case 8: hipLaunchKernelGGL((attn_oproj_kernel<WT, NPL, 8>), grid, dim3(kThreads), oproj_lds<NPL>(), s, a, ns); break;
+        case 16: hipLaunchKernelGGL((attn_oproj_kernel<WT, NPL, 16>), grid, dim3(kThreads), oproj_lds<NPL>(), s, a, ns); break;
+        case 24: hipLaunchKernelGGL((attn_oproj_kernel<WT, NPL, 24>), grid, dim3(kThreads), oproj_lds<NPL>(), s, a, ns); break;
+        default: hipLaunchKernelGGL((attn_oproj_kernel<WT, NPL, 32>), grid, dim3(kThreads), oproj_lds<NPL>(), s, a, ns); break;
+    }
+}
+template <typename WT>
+void oproj2_launch_nb(const OprojArgs& a, int ns, dim3 grid, hipStream_t s) {
+    switch (oproj_bucket(a.nact)) {
+        case 0: hipLaunchKernelGGL((attn_oproj2_kernel<WT, 8, 0>), grid, dim3(kThreads), oproj2_lds<8>(), s, a, ns); break;
+        case 8: hipLaunchKernelGGL((attn_oproj2_kernel<WT, 8, 8>), grid, dim3(kThreads), oproj2_lds<8>(), s, a, ns); break;
+        case 16: hipLaunchKernelGGL((attn_oproj2_kernel<WT, 8, 16>), grid, dim3(kThreads), oproj2_lds<8>(), s, a, ns); break;
+        case 24: hipLaunchKernelGGL((attn_oproj2_kernel<WT, 8, 24>), grid, dim3(kThreads), oproj2_lds<8>(), s, a, ns); break;
+        default: hipLaunchKernelGGL((attn_oproj2_kernel<WT, 8, 32>), grid, dim3(kThreads), oproj2_lds<8>(), s, a, ns); break;
+    }
+}
+
 template <typename WT>
 int oproj_launch_w(const OprojArgs& a, hipStream_t s) {
     // ~1024 workgroups: rows per workgroup = 16 * NPL
@@ -132,21 +155,23 @@ int oproj_launch_w(const OprojArgs& a, hipStream_t s) {
     // fp16 weights only: the int8 form needs 92 VGPRs with two heads (68 with one), so 13B's
     // 1,600 workgroups no longer fit in one round and it measured 0.7-0.9 us slower (r06q); fp32
     // weights (the parity instantiation) would need 140
-    if (LLMI_OPROJ_HG == 2 && sizeof(WT) == 2 && a.heads % 2 == 0 && !a.head_major && npl == 8) {
-        const dim3 grid2(a.heads / 2, (a.n_rows + 8 * npl - 1) / (8 * npl));
-        hipLaunchKernelGGL((attn_oproj2_kernel<WT, 8>), grid2, dim3(kThreads), oproj2_lds<8>(), s, a, ns);
-        LLMI_HIP(hipGetLastError());
-        return LLMI_OK;
+    if constexpr (LLMI_OPROJ_HG == 2 && sizeof(WT) == 2) {
+        if (a.heads % 2 == 0 && !a.head_major && npl == 8) {
+            const dim3 grid2(a.heads / 2, (a.n_rows + 8 * npl - 1) / (8 * npl));
+            oproj2_launch_nb<WT>(a, ns, grid2, s);
+            LLMI_HIP(hipGetLastError());
+            return LLMI_OK;
+        }
     }
     const dim3 grid(a.heads, (a.n_rows + 16 * npl - 1) / (16 * npl));
     switch (npl) {
 #if LLMI_OPROJ_NPL == 16
-        case 16: hipLaunchKernelGGL((attn_oproj_kernel<WT, 16>), grid, dim3(kThreads), oproj_lds<16>(), s, a, ns); break;
+        case 16: oproj_launch_nb<WT, 16>(a, ns, grid, s); break;
 #endif
-        case 8: hipLaunchKernelGGL((attn_oproj_kernel<WT, 8>), grid, dim3(kThreads), oproj_lds<8>(), s, a, ns); break;
-        case 4: hipLaunchKernelGGL((attn_oproj_kernel<WT, 4>), grid, dim3(kThreads), oproj_lds<4>(), s, a, ns); break;
-        case 2: hipLaunchKernelGGL((attn_oproj_kernel<WT, 2>), grid, dim3(kThreads), oproj_lds<2>(), s, a, ns); break;
-        default: hipLaunchKernelGGL((attn_oproj_kernel<WT, 1>), grid, dim3(kThreads), oproj_lds<1>(), s, a, ns); break;
+        case 8: oproj_launch_nb<WT, 8>(a, ns, grid, s); break;
+        case 4: oproj_launch_nb<WT, 4>(a, ns, grid, s); break;
+        case 2: oproj_launch_nb<WT, 2>(a, ns, grid, s); break;
+        default: oproj_launch_nb<WT, 1>(a, ns, grid, s); break;
     }
     LLMI_HIP(hipGetLastError());
     return LLMI_OK;

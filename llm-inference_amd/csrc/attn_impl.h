@@ -611,7 +611,22 @@ __device__ __forceinline__ void oproj_load_w(const OprojArgs& a, int h, int chun
     }
 }
 
-template <typename WT, int NPL, typename IO>
+// Split bucket of a host-sized launch (OprojArgs::nact > 0, one captured step per split count):
+// NB = 8, 16, 24 or 32 register-held partials per head dim, NB - 8 < min(nact, 32) <= NB. Slots
+// below NB - 8 are live in every launch of the bucket: plain loads and FMAs, no select. Each of
+// the last eight loads is skipped on a uniform (scalar) compare with nact, so a launch issues its
+// nact partial loads and none for the dead slots -- they used to re-load split 0 in front of the
+// W_o stream (16 of 32 at ctx 1024, 31 at ctx <= 64) -- and their FMAs keep the selects, in an
+// unguarded block (FMAs under the same guard let the compiler sink the loads to them, behind the
+// first wait). Same operands, same order as before; a dead slot's fmaf(0, 0, O) that no longer
+// runs moves no xacc bit. NB = 0 is the position-derived form (the operator API's a.nact <= 0):
+// every slot loaded, selects decide.
+constexpr int kOvMax = 2 * kMergeChunk;
+constexpr int oproj_bucket(int nact) { return nact <= 0 ? 0 : nact >= kOvMax ? kOvMax : (nact + 7) / 8 * 8; }
+template <int NB>
+__device__ __forceinline__ bool oproj_live(int slot, int n) { return NB == 0 || slot < NB - 8 || slot < n; }
+
+template <typename WT, int NPL, typename IO, int NB = 0>
 __device__ __forceinline__ void oproj_body(const OprojArgs& a, int h, int chunk, int ns, float* smem) {
     float* m_s = smem;
     float* l_s = m_s + kMaxSplits;
@@ -628,7 +643,8 @@ __device__ __forceinline__ void oproj_body(const OprojArgs& a, int h, int chunk,
     const int d = tid % D, half = tid / D;
     const float* mlh = ws.ml + (size_t)h * ns * 2;
     const float* oh = ws.o + (size_t)h * ns * D + d;
-    float ov[kMergeChunk];
+    constexpr int kLd = NB ? NB / 2 : kMergeChunk;  // this thread's slots: splits half + 2 i
+    float ov[kLd];
     // splits to load: the host-known active count, else every split (the position
     // decides which are used)
     const int nl = a.nact > 0 ? min(a.nact, ns) : ns;
@@ -641,18 +657,18 @@ __device__ __forceinline__ void oproj_body(const OprojArgs& a, int h, int chunk,
     // serialised the partials' latency in front of the W_o stream)
     {
 #pragma unroll
-    for (int i = 0; i < kMergeChunk; ++i) {
+    for (int i = 0; i < kLd; ++i) {
         const int sp = half + 2 * i;
-        ov[i] = IO::ld(oh + (size_t)(sp < nl ? sp : 0) * D);
+        ov[i] = 0.f;
+        if (oproj_live<NB>(2 * i, nl)) ov[i] = IO::ld(oh + (size_t)(sp < nl ? sp : 0) * D);
     }
     constexpr int kMlPer = kMaxSplits / kThreads;
-    float mr[kMlPer], lr[kMlPer];
+    float2 ml[kMlPer];  // (m, l) of a split: one 8-byte load
 #pragma unroll
     for (int i = 0; i < kMlPer; ++i) {
         if (i * kThreads < nl) {  // uniform branch: no per-lane predication of the loads
             const int sp = min(tid + i * kThreads, nl - 1);
-            mr[i] = IO::ld(mlh + 2 * sp);
-            lr[i] = IO::ld(mlh + 2 * sp + 1);
+            ml[i] = IO::ld2(reinterpret_cast<const float2*>(mlh + 2 * sp));
         }
     }
     load_w();
@@ -660,12 +676,12 @@ __device__ __forceinline__ void oproj_body(const OprojArgs& a, int h, int chunk,
     for (int i = 0; i < kMlPer; ++i) {
         const int sp = tid + i * kThreads;
         if (i * kThreads < nl && sp < nl) {
-            m_s[sp] = mr[i];
-            l_s[sp] = lr[i];
+            m_s[sp] = ml[i].x;
+            l_s[sp] = ml[i].y;
         }
     }
     int nact = nl;
-    if (a.nact <= 0) {  // position-derived split count (its load waits here, after the W_o issue)
+    if (NB == 0 && a.nact <= 0) {  // position-derived split count (its load waits here, after the W_o issue)
         const int pos = a.pos_dev ? *a.pos_dev : a.pos_host;
         if (pos < 0 || pos >= a.max_seq) return;
         nact = (pos + 1 + CH - 1) / CH;
@@ -688,11 +704,13 @@ __device__ __forceinline__ void oproj_body(const OprojArgs& a, int h, int chunk,
     __syncthreads();
     float O = 0.f;
 #pragma unroll
-    for (int i = 0; i < kMergeChunk; ++i) {
+    for (int i = 0; i < kLd; ++i) {
         const int sp = half + 2 * i;
-        O = fmaf(sp < nact ? ov[i] : 0.f, sp < nact ? m_s[sp] : 0.f, O);
+        if (NB && 2 * i + 1 < NB - 8) O = fmaf(ov[i], m_s[sp], O);
+        else O = fmaf(sp < nact ? ov[i] : 0.f, sp < nact ? m_s[sp] : 0.f, O);
     }
-    for (int sp = half + 2 * kMergeChunk; sp < nact; sp += 2) O = fmaf(IO::ld(oh + (size_t)sp * D), m_s[sp], O);
+    if constexpr (NB == 0 || NB == kOvMax)
+        for (int sp = half + 2 * kMergeChunk; sp < nact; sp += 2) O = fmaf(IO::ld(oh + (size_t)sp * D), m_s[sp], O);
     o_red[half][d] = O;
     __syncthreads();
     if (tid < D) o_s[tid] = (o_red[0][tid] + o_red[1][tid]) * linv_s;
@@ -759,8 +777,14 @@ __device__ __forceinline__ float ld_wt(const float* p) {
     return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED,
                                              __HIP_MEMORY_SCOPE_AGENT));
 }
+__device__ __forceinline__ float2 ld_wt2(const float* p) {  // 8-byte aligned pair
+    const unsigned long long u = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED,
+                                                   __HIP_MEMORY_SCOPE_AGENT);
+    return make_float2(__uint_as_float((unsigned)u), __uint_as_float((unsigned)(u >> 32)));
+}
 
-template <typename WT, int NPL, typename IO, bool FUSED = false>
+// NB: the split bucket of a host-sized launch (see oproj_body); here a thread holds all NB slots.
+template <typename WT, int NPL, typename IO, bool FUSED = false, int NB = 0>
 __device__ __forceinline__ void oproj_body2(const OprojArgs& a, int hp, int chunk, int ns, float* smem) {
     float* m_s = smem;                      // [2][kMaxSplits]
     float* l_s = m_s + 2 * kMaxSplits;      // [2][kMaxSplits]
@@ -778,11 +802,13 @@ __device__ __forceinline__ void oproj_body2(const OprojArgs& a, int hp, int chun
     const int mh = tid >> 7, d = tid & (D - 1);  // merge: thread (head mh of the pair, dim d)
     const float* mlh = ws.ml + (size_t)(2 * hp + mh) * ns * 2;
     const float* oh = ws.o + (size_t)(2 * hp + mh) * ns * D + d;
-    constexpr int kOv = 2 * kMergeChunk;
-    float ov[kOv];
+    constexpr int kOv = kOvMax;
+    constexpr int kLd = NB ? NB : kOv;
+    static_assert(NB % 2 == 0, "the merge pairs an even and an odd split per step");
+    float ov[kLd];
     const int nl = a.nact > 0 ? min(a.nact, ns) : ns;
     constexpr int kMlPer = kMaxSplits / (kThreads / 2);
-    float mr[kMlPer], lr[kMlPer];
+    float2 ml[kMlPer];  // (m, l) of a split: one 8-byte load
     W8<WT> wr[NPL];
     auto load_w = [&]() {
 #pragma unroll
@@ -801,6 +827,22 @@ __device__ __forceinline__ void oproj_body2(const OprojArgs& a, int hp, int chun
         }
     };
     auto ld_p = [&](const float* p) { return FUSED ? ld_wt(p) : IO::ld(p); };
+    auto ld_p2 = [&](const float* p) { return FUSED ? ld_wt2(p) : IO::ld2(reinterpret_cast<const float2*>(p)); };
+    // FUSED: a workgroup's departure; the pair's last workgroup re-zeroes both arrival counters and
+    // the departure counter. A workgroup that gives up waiting departs too, or the counters would
+    // keep this launch's arrivals and let the next fused launch through before its partials exist.
+    auto depart = [&]() {
+        if (tid == 0) {
+            unsigned* arr0 = ws.counters + (size_t)(2 * hp) * kCntWordsPerHead;
+            const int n_chunks = (a.n_rows + 8 * NPL - 1) / (8 * NPL);
+            if (atomicAdd(arr0 + 1, 1u) == (unsigned)(n_chunks - 1)) {
+                __hip_atomic_store(arr0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(arr0 + kCntWordsPerHead, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(arr0 + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    };
+    (void)depart;
     if constexpr (FUSED) {
         load_w();
         unsigned* arr0 = ws.counters + (size_t)(2 * hp) * kCntWordsPerHead;
@@ -818,17 +860,22 @@ __device__ __forceinline__ void oproj_body2(const OprojArgs& a, int hp, int chun
             linv_s[2] = dead ? 1.f : 0.f;
         }
         __syncthreads();
-        if (linv_s[2] != 0.f) return;
+        if (linv_s[2] != 0.f) {
+            depart();
+            return;
+        }
     }
     // issue order as oproj_body: partials, (m, l), then the W_o slices, before any wait
 #pragma unroll
-    for (int i = 0; i < kOv; ++i) ov[i] = ld_p(oh + (size_t)(i < nl ? i : 0) * D);
+    for (int i = 0; i < kLd; ++i) {
+        ov[i] = 0.f;
+        if (oproj_live<NB>(i, nl)) ov[i] = ld_p(oh + (size_t)(i < nl ? i : 0) * D);
+    }
 #pragma unroll
     for (int i = 0; i < kMlPer; ++i) {
         if (i * (kThreads / 2) < nl) {
             const int sp = min(d + i * (kThreads / 2), nl - 1);
-            mr[i] = ld_p(mlh + 2 * sp);
-            lr[i] = ld_p(mlh + 2 * sp + 1);
+            ml[i] = ld_p2(mlh + 2 * sp);
         }
     }
     if constexpr (!FUSED) load_w();
@@ -836,12 +883,12 @@ __device__ __forceinline__ void oproj_body2(const OprojArgs& a, int hp, int chun
     for (int i = 0; i < kMlPer; ++i) {
         const int sp = d + i * (kThreads / 2);
         if (i * (kThreads / 2) < nl && sp < nl) {
-            m_s[mh * kMaxSplits + sp] = mr[i];
-            l_s[mh * kMaxSplits + sp] = lr[i];
+            m_s[mh * kMaxSplits + sp] = ml[i].x;
+            l_s[mh * kMaxSplits + sp] = ml[i].y;
         }
     }
     int nact = nl;
-    if (a.nact <= 0) {
+    if (NB == 0 && a.nact <= 0) {
         const int pos = a.pos_dev ? *a.pos_dev : a.pos_host;
         if (pos < 0 || pos >= a.max_seq) return;
         nact = (pos + 1 + CH - 1) / CH;
@@ -871,31 +918,27 @@ __device__ __forceinline__ void oproj_body2(const OprojArgs& a, int hp, int chun
         const float* mw = m_s + mh * kMaxSplits;
         float O0 = 0.f, O1 = 0.f;
 #pragma unroll
-        for (int i = 0; i < kMergeChunk; ++i) {
+        for (int i = 0; i < kLd / 2; ++i) {
             const int s0 = 2 * i, s1 = 2 * i + 1;
-            O0 = fmaf(s0 < nact ? ov[s0] : 0.f, s0 < nact ? mw[s0] : 0.f, O0);
-            O1 = fmaf(s1 < nact ? ov[s1] : 0.f, s1 < nact ? mw[s1] : 0.f, O1);
+            if (NB && s1 < NB - 8) {  // live in every launch of the bucket
+                O0 = fmaf(ov[s0], mw[s0], O0);
+                O1 = fmaf(ov[s1], mw[s1], O1);
+            } else {
+                O0 = fmaf(s0 < nact ? ov[s0] : 0.f, s0 < nact ? mw[s0] : 0.f, O0);
+                O1 = fmaf(s1 < nact ? ov[s1] : 0.f, s1 < nact ? mw[s1] : 0.f, O1);
+            }
         }
-        for (int sp = kOv; sp < nact; sp += 2) {
-            O0 = fmaf(ld_p(oh + (size_t)sp * D), mw[sp], O0);
-            if (sp + 1 < nact) O1 = fmaf(ld_p(oh + (size_t)(sp + 1) * D), mw[sp + 1], O1);
+        if constexpr (NB == 0 || NB == kOv) {
+            for (int sp = kOv; sp < nact; sp += 2) {
+                O0 = fmaf(ld_p(oh + (size_t)sp * D), mw[sp], O0);
+                if (sp + 1 < nact) O1 = fmaf(ld_p(oh + (size_t)(sp + 1) * D), mw[sp + 1], O1);
+            }
         }
         o_s[mh * D + d] = (O0 + O1) * linv_s[mh];
     }
     __syncthreads();
-    if constexpr (FUSED) {
-        // every partial of this workgroup is read (the barrier above): depart; the pair's last
-        // workgroup re-zeroes both arrival counters and the departure counter
-        if (tid == 0) {
-            unsigned* arr0 = ws.counters + (size_t)(2 * hp) * kCntWordsPerHead;
-            const int n_chunks = (a.n_rows + 8 * NPL - 1) / (8 * NPL);
-            if (atomicAdd(arr0 + 1, 1u) == (unsigned)(n_chunks - 1)) {
-                __hip_atomic_store(arr0, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(arr0 + kCntWordsPerHead, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(arr0 + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
+    // every partial of this workgroup is read (the barrier above): depart
+    if constexpr (FUSED) depart();
     float* yh = y_s + hs * 8 * NPL;
     const float* oh_s = o_s + hs * D;
     if constexpr (sizeof(WT) == 1 && NPL >= 2) {

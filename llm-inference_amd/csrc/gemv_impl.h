@@ -236,6 +236,7 @@ __device__ __forceinline__ void gemv_body(const GemvArgs& a, int bid, int nblk, 
             // head-major order (a.tag_heads > 0, MHA): group g of head h's q, k, v rows in turn,
             // so a head's rows finish together and its attention can start while later heads'
             // rows stream (64 two-row groups per 128-row head block)
+            static_assert(!TAG || ROWS == 2, "the head-major remap counts 64 two-row groups per 128-row head block");
             if (a.tag_heads > 0) {
                 const int h = g / 192, rem = g - 192 * h, t = rem >> 6;
                 g = t * a.tag_heads * 64 + h * 64 + (rem & 63);
