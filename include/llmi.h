@@ -291,7 +291,9 @@ int llmi_debug_prefill_stamps(void* stamps);
  * cache_dtype (f16 / f32); rope_tab [max_seq][64] (cos, sin) fp32 pairs; out [m, heads * 128].
  * mfma_planes 0: the scalar kernel; 1 / 2 (fp16 cache): the MFMA kernel with that many fp16
  * planes, its output in `out` or, with out_hi (, out_lo), as fp16 planes [m, heads * 128]
- * (out_lo8: out_lo rows hold e4m3 bytes of lo * 2^12 in their first half). split_ws
+ * (out_lo8: out_lo rows hold e4m3 bytes of lo * 2^12 in their first half). q8_planes 1 / 2
+ * (int8 cache with k_scale, v_scale; mfma_planes 0, out_lo8 0): the int8 MFMA kernel, the same
+ * outputs, chunks and plan as the fp16 MFMA kernel; 0 with an int8 cache: the scalar kernel. split_ws
  * (split_ws_floats fp32 elements): scratch for split-key partials; chunk_blocks > 0 with
  * split_ws: 64-key blocks per chunk instead of the automatic choice. The caller owns every buffer.
  * llmi_debug_prefill_attn_plan launches nothing: it runs the same argument checks and the
@@ -316,8 +318,9 @@ typedef struct llmi_debug_prefill_attn_args {
     float* split_ws;
     size_t split_ws_floats;
     int chunk_blocks;
-    void* k_scale; /* cache_dtype LLMI_I8 (KV8, the scalar kernel only): the layer's fp16 row scales */
+    void* k_scale; /* cache_dtype LLMI_I8 (KV8): the layer's fp16 row scales */
     void* v_scale; /* [kv_heads, max_seq]; NULL: unused (an f16 / f32 cache) */
+    int q8_planes; /* int8 cache: 0 the scalar kernel; 1 / 2 the int8 MFMA kernel with that many planes */
 } llmi_debug_prefill_attn_args;
 int llmi_debug_prefill_attn(const llmi_debug_prefill_attn_args* args, llmi_stream_t stream);
 int llmi_debug_prefill_attn_plan(const llmi_debug_prefill_attn_args* args, int* cb, int* maxc, int* grid,

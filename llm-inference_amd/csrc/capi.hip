@@ -262,6 +262,7 @@ PrefillAttnArgs debug_prefill_attn_args(const llmi_debug_prefill_attn_args& d) {
     a.out_lo8 = d.out_lo8; a.split_ws = d.split_ws; a.split_ws_floats = d.split_ws_floats;
     a.chunk_blocks = d.chunk_blocks;
     a.k_scale = static_cast<__half*>(d.k_scale); a.v_scale = static_cast<__half*>(d.v_scale);
+    a.q8_planes = d.q8_planes;
     return a;
 }
 }  // namespace

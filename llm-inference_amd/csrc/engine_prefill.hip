@@ -115,10 +115,13 @@ int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     if (c.kv_dtype == LLMI_F16) {  // MFMA attention writes the o_proj input planes itself
         pa.mfma_planes = split >= 2 ? 2 : 1; pa.out_hi = pf_ah; pa.out_lo = lo; pa.out_lo8 = f8 ? 1 : 0;
         pa.split_ws = pf_split; pa.split_ws_floats = pf_split_floats;
+    } else if (c.kv_dtype == LLMI_I8) {  // so does the int8 cache's (split 3 never gets here: lo8_supported)
+        pa.q8_planes = split >= 2 ? 2 : 1; pa.out_hi = pf_ah; pa.out_lo = lo;
+        pa.split_ws = pf_split; pa.split_ws_floats = pf_split_floats;
     }
     LLMI_TRY(prefill_attn_launch(pa, stream));
     // o_proj + residual
-    if (c.kv_dtype != LLMI_F16)
+    if (c.kv_dtype != LLMI_F16 && c.kv_dtype != LLMI_I8)
         LLMI_TRY(rows_split_launch(pf_o, ql, m, ql, nullptr, edt, 0.f, pf_ah, lo, ql, stream, nullptr, 0, f8));
     // split-K into slabs (128 tiles alone would leave half the CUs idle); the next
     // rows_split adds the slices into x in slice order (deterministic). The fp8 lo
@@ -282,7 +285,12 @@ int Engine::prefill(int n, int split, bool scored) {
             g.epi = EPI_STORE; g.y = pf_qkv; g.ldy = g.n;
             LLMI_TRY(gemm_launch(g, stream));
             // rope + kv write + causal attention
-            LLMI_TRY(prefill_attn_launch(prefill_attn_args(l, m, p0), stream));
+            PrefillAttnArgs pa = prefill_attn_args(l, m, p0);
+            if (c.kv_dtype == LLMI_I8) {  // the MFMA attention over the int8 rows, fp32 rows out
+                pa.q8_planes = g.split >= 2 ? 2 : 1;
+                pa.split_ws = pf_split; pa.split_ws_floats = pf_split_floats;
+            }
+            LLMI_TRY(prefill_attn_launch(pa, stream));
             // o_proj + residual
             g.a = pf_o; g.lda = ql; g.gamma = nullptr;
             g.w = L.o; g.scales = L.o_s; g.n = H; g.k = ql;

@@ -291,7 +291,7 @@ struct PrefillAttnArgs {
     const float* qkv2 = nullptr;   // optional second K slice of qkv (same layout), added first
     void* k_cache = nullptr;       // layer base [kv_heads, max_seq, D]
     void* v_cache = nullptr;
-    int cache_dtype = LLMI_F16;    // LLMI_I8 (KV8): the scalar form only, with the scales below
+    int cache_dtype = LLMI_F16;    // LLMI_I8 (KV8): the scalar form or q8_planes, with the scales below
     __half* k_scale = nullptr;     // int8 cache: layer base [kv_heads, max_seq] fp16 row scales
     __half* v_scale = nullptr;
     int max_seq = 0;
@@ -311,12 +311,16 @@ struct PrefillAttnArgs {
     // > 0 with split_ws: key blocks (64 keys) per chunk instead of the automatic choice (as
     // LLMI_PF_CHUNK; llmi_debug_prefill_attn). The engine leaves it 0.
     int chunk_blocks = 0;
+    // int8 cache only (mfma_planes 0, no out_lo8): 1 or 2 = attn_prefill_q8_kernel, the MFMA form
+    // over the int8 rows, with that many fp16 planes of q and p; outputs, split_ws and the
+    // chunk plan as for mfma_planes. 0: the scalar form.
+    int q8_planes = 0;
 };
 int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s);
 // what prefill_attn_launch would run for a, nothing launched (the launcher calls it too): cb
 // key blocks per chunk, maxc chunk slots per query block (1: no partials), the attention
 // kernel's workgroups and the merge instance (0: no merge launch, else 2, 4 or 8 slots). The
-// scalar form (mfma_planes 0) reports cb 0, maxc 1, merge_slots 0.
+// scalar form (mfma_planes 0 and q8_planes 0) reports cb 0, maxc 1, merge_slots 0.
 struct PrefillAttnPlan {
     int cb = 0, maxc = 1, grid = 0, merge_slots = 0;
 };

@@ -282,6 +282,14 @@ __global__ __launch_bounds__(kThreads) void attn_prefill_kernel(const float* qkv
 // is the fp16 throughput mode. Output: fp32 rows, or the o_proj GEMM's fp16 input planes.
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
+// attn_prefill_q8_kernel is compiled without the packed fp32 VALU forms; a function is inlined only
+// into callers that have all its target features, so the two helpers it shares carry the mark too
+// (inlined into the other kernels they compile as before) and it calls no header function
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PF_NOPK __attribute__((target("no-packed-fp32-ops")))
+#else
+#define PF_NOPK
+#endif
 constexpr int QM = 64;  // query rows per workgroup
 constexpr int KB = 64;  // keys per block
 
@@ -301,7 +309,7 @@ inline int pf_rope_threads() {
     }();
     return v;
 }
-__host__ __device__ inline int pf_nkb(int qb, int p0, int m_rows) {
+__host__ __device__ PF_NOPK inline int pf_nkb(int qb, int p0, int m_rows) {
     const int kend = p0 + (qb * QM + QM < m_rows ? qb * QM + QM : m_rows);
     return (kend + KB - 1) / KB;
 }
@@ -358,7 +366,7 @@ __device__ __forceinline__ float xsum32(float x) {
 }
 // global_load_lds_dwordx4 with a uniform base (SGPRs) and a per-lane 32-bit byte offset:
 // the wave's 64 lanes fill 1 KB of LDS from `lds` on, lane-linear
-__device__ __forceinline__ void pf_glds(const void* sbase, unsigned voff, unsigned lds) {
+__device__ __forceinline__ PF_NOPK void pf_glds(const void* sbase, unsigned voff, unsigned lds) {
     unsigned keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
@@ -661,6 +669,389 @@ __global__ __launch_bounds__(kTrThreads) void attn_prefill_tr_kernel(const float
     }
 }
 
+// ---- MFMA form for the int8 cache (KV8): attn_prefill_q8_kernel. A cached value is an integer in
+// [-127, 127], exact in fp16, so K and V go to the fp16 matrix cores unrounded and the rows' fp16
+// scales are applied outside the products: score_j = s_k[j] * sum q k8 (the decode kernel's
+// expression) and O = sum (p_j s_v[j]) v8_j. With P = 2 planes of q and of p the result is as
+// fp32-faithful as the fp16-cache kernel's. The work split, the lazy log2 softmax, the grid and the
+// partial format are attn_prefill_tr_kernel's (so the merge kernel and the chunk plan serve both);
+// the staging, the operand reads and the scale handling are this kernel's own:
+//
+// LDS. A 64-key int8 image is 8 KB in 128-B rows; a stage is [K image | V image | 64 + 64 scales],
+// 16.5 KB, and the ring has kQ8Stages = 4 of them worked in pairs (the pair being computed, the
+// next pair in flight, one barrier per pair): 67 584 B. The 32-KB fp32 q image goes through stages
+// 2 and 3, which the first pair leaves free; the epilogue's half-combine image (33.5 KB, combined
+// in place) reuses the ring. Two workgroups fit a CU's 160 KB (at most 128 VGPRs each, see
+// __launch_bounds__), against one for the fp16 kernel's 128 KB.
+// Copies. Wave w fills 1-KB span w of both images (rows 8 w .. 8 w + 7) with one
+// global_load_lds_dwordx4 each: lane -> row 8 w + lane / 8, physical 16-B chunk lane % 8 = logical
+// chunk ^ swizzle(row). Waves 0 / 1 add one global_load_lds_ushort for the block's k / v scales:
+// lane = row, landing zero-extended in dword lane of the stage's side array (measured: the
+// sub-dword copy keeps the 4-byte lane stride). 2 (+ 1) copies per wave and block, all counted by
+// the same vmcnt(0) before the pair's barrier. Source rows are clamped to kend - 1, so no byte and
+// no scale of a row at or past the keys' end is ever loaded.
+// K operand. Lane (fr, fq) of tile j reads the 8 bytes of dims 32 ks + 8 fq .. + 7 of image row
+// 32 kp + 16 j + fr (key order inside a tile is the identity). Chunk c of row r sits at
+// c ^ ((r >> 1) & 7): a 32-lane half reads 16 rows x one chunk (two 8-B halves), the 8 even rows
+// on 8 distinct chunks of the lower 32 banks and the odd rows on the upper 32 -- conflict-free.
+// int8 -> fp16 by the bias trick: b ^ 0x80 is b + 128 in [0, 255], 0x6400 | that is the fp16
+// 1024 + (b + 128) exactly, minus 1152 is b. Per 4 bytes the compiler emits 1 v_xor_b32,
+// 2 v_perm_b32 and 2 v_pk_add_f16 (5 VALU ops; sign-extend + convert + pack is 10).
+// V operand. ds_read_b64_tr_b8: in each 16-lane group lane i supplies 8 bytes of row i / 2
+// (half i % 2 of a 16-B chunk) and receives column i of that 8 x 16 byte matrix -- 8 keys of one
+// dim, the k order of the 16-bit operand once converted (measured on gfx950). Group fq supplies
+// image rows 32 kp + 16 (r >> 2) + 4 fq + (r & 3), r = i / 2: exactly the keys of its P^T
+// elements (accumulator rows 4 fq + e of tiles 0, 1), so no key permutation is needed. Chunk c of
+// row r sits at c ^ (((r >> 1) & 3) | ((r >> 4) & 1) << 2): a 32-lane half reads rows
+// {0..7, 16..23} or {8..15, 24..31} of the key half, again 8 distinct chunks per bank half.
+// Scales and range. p <= 256 under the lazy reference and an fp16 scale reaches 65504, so the
+// planes carry p_j s_v[j] 128 / v_ref with v_ref a power of two >= every v scale the wave has
+// seen (raised when exceeded, with o[] rescaled in the softmax's own rescale pass, never lowered):
+// plane values stay <= 2^15 and the division is exact. The epilogue multiplies o[] by v_ref / 128
+// before the halves combine, so the output and the merge partials are in the fp16 kernel's units.
+// Every finite fp16 scale is supported (row amplitudes up to 127 * 65504); rows whose scale is
+// more than ~2^20 below the largest lose relative, not absolute, precision. A key masked for a
+// lane's query contributes exactly 0 by a select, whatever its scale (a NaN-scale row at a later
+// position cannot reach an earlier query); a visible NaN scale makes the query's output NaN, as in
+// the scalar form.
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute push(__attribute__((target("no-packed-fp32-ops"))), apply_to = function)
+#endif
+typedef int i2v __attribute__((ext_vector_type(2)));
+typedef unsigned u4v __attribute__((ext_vector_type(4)));
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+constexpr int kQ8Stages = 4;
+constexpr int kQ8Img = KB * D;                  // one 64-key int8 image: 8 KB
+constexpr int kQ8Stage = 2 * kQ8Img + 2 * KB * 4;  // K, V, then a dword per k and per v scale
+__device__ __forceinline__ int q8_kswz(int r) { return (r >> 1) & 7; }
+__device__ __forceinline__ int q8_vswz(int r) { return ((r >> 1) & 3) | (((r >> 4) & 1) << 2); }
+__device__ __forceinline__ void pf_glds_u16(const void* sbase, unsigned voff, unsigned lds) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_ushort %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "v"(voff), "s"(sbase), "s"(lds)
+                 : "memory");
+}
+// 8 int8 (two dwords) -> 8 fp16, exactly (the bias trick above)
+__device__ __forceinline__ h8 q8_h8(i2v b) {
+    const h2 bias = {(_Float16)1152.f, (_Float16)1152.f};
+    h2 r[4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const unsigned u = (unsigned)b[i] ^ 0x80808080u;
+        r[2 * i] = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, u, 0x04010400u)) - bias;
+        r[2 * i + 1] = __builtin_bit_cast(h2, __builtin_amdgcn_perm(0x64646464u, u, 0x04030402u)) - bias;
+    }
+    return h8{r[0][0], r[0][1], r[1][0], r[1][1], r[2][0], r[2][1], r[3][0], r[3][1]};
+}
+__device__ __forceinline__ float q8_scale(unsigned dw) { return (float)__builtin_bit_cast(_Float16, (unsigned short)dw); }
+__device__ __forceinline__ unsigned q8_bits(float x) { return __builtin_bit_cast(unsigned, x); }
+__device__ __forceinline__ float q8_float(unsigned x) { return __builtin_bit_cast(float, x); }
+__device__ __forceinline__ int q8_min(int a, int b) { return a < b ? a : b; }
+// x as the fp32 value in a register: a plane's lo must be the remainder of the hi that is stored.
+// Left visible as a product, the compiler converts one use with v_fma_mixlo_f16 (the exact product
+// rounded once) and the other from the rounded fp32 product, an fp16 ulp apart at a double-rounding
+// tie (measured: single (row, head) pairs at 1.5e-4 instead of 2e-7)
+__device__ __forceinline__ float q8_rounded(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+__device__ __forceinline__ void q8_sync() {  // __syncthreads, spelled out
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// over the lane's four 16-lane groups (permlane swaps, as xmax16 / xmax32 and xsum16 / xsum32)
+__device__ __forceinline__ float q8_xmax(float x) {
+    auto r = __builtin_amdgcn_permlane16_swap(q8_bits(x), q8_bits(x), false, false);
+    x = __builtin_fmaxf(q8_float(r[0]), q8_float(r[1]));
+    r = __builtin_amdgcn_permlane32_swap(q8_bits(x), q8_bits(x), false, false);
+    return __builtin_fmaxf(q8_float(r[0]), q8_float(r[1]));
+}
+__device__ __forceinline__ float q8_xsum(float x) {
+    auto r = __builtin_amdgcn_permlane16_swap(q8_bits(x), q8_bits(x), false, false);
+    x = q8_float(r[0]) + q8_float(r[1]);
+    r = __builtin_amdgcn_permlane32_swap(q8_bits(x), q8_bits(x), false, false);
+    return q8_float(r[0]) + q8_float(r[1]);
+}
+
+template <int P>
+__global__ __launch_bounds__(kTrThreads, 4) void attn_prefill_q8_kernel(  // 4 waves a SIMD: 2 workgroups a CU
+    const float* qkv, int ld, int m_rows, int p0, int heads, int kv_heads, const int8_t* k_cache, const int8_t* v_cache,
+    const __half* k_scale, const __half* v_scale, int max_seq, float* out, _Float16* out_hi, _Float16* out_lo, int ldo,
+    int cb, float* ws, int maxc) {
+    __shared__ __attribute__((aligned(16))) char smem[kQ8Stages * kQ8Stage];
+    const int t = __builtin_amdgcn_workitem_id_x(), lane = t & 63;
+    const int w = __builtin_amdgcn_readfirstlane(t >> 6);  // in an SGPR
+    const int fr = lane & 15, fq = lane >> 4;
+    const int qt = w & 3, kp = w >> 2;  // query tile, key half
+
+    // (query block, chunk, head) of this workgroup: attn_prefill_tr_kernel's enumeration
+    const int nqb = (m_rows + QM - 1) / QM;
+    const int wg = __builtin_amdgcn_workgroup_id_x(), xcd = wg & 7, r = wg >> 3;
+    const int per = (heads - xcd + 7) / 8;
+    int items = 0;
+    for (int q = 0; q < nqb; ++q) items += (pf_nkb(q, p0, m_rows) + cb - 1) / cb;
+    if (r >= per * items) return;
+    const int h = xcd + 8 * (r % per);
+    int qb = nqb - 1, chunk = 0, nch = 1;
+    for (int idx = r / per; qb >= 0; --qb) {
+        nch = (pf_nkb(qb, p0, m_rows) + cb - 1) / cb;
+        if (idx < nch) {
+            chunk = idx;
+            break;
+        }
+        idx -= nch;
+    }
+    const int kvh = h / (heads / kv_heads);
+    const int q_first = qb * QM;
+    const float qscale = 1.4426950408889634f / __builtin_sqrtf((float)D);  // log2(e) / sqrt(d)
+
+    h8 qa[P][4];
+    const int kend = p0 + q8_min(q_first + QM, m_rows);
+    const int nkb = (kend + KB - 1) / KB;
+    const int kb0 = chunk * cb, kb1 = q8_min(kb0 + cb, nkb);
+    const void* kc = k_cache + (size_t)kvh * max_seq * D;
+    const void* vc = v_cache + (size_t)kvh * max_seq * D;
+    const void* sc = (w == 0 ? k_scale : v_scale) + (size_t)kvh * max_seq;  // the scale copy of waves 0, 1
+    const unsigned lds0 = (unsigned)(uintptr_t)smem;
+    const int nit = kb1 - kb0;  // iteration i computes key block kb0 + i
+    auto issue = [&](int it) {
+        const int kb = kb0 + it;
+        const unsigned sb = lds0 + (unsigned)(it % kQ8Stages) * kQ8Stage;
+        const int row = 8 * w + (lane >> 3), cp = lane & 7;
+        const unsigned src = (unsigned)q8_min(kb * KB + row, kend - 1) * (unsigned)D;
+        const unsigned dst = __builtin_amdgcn_readfirstlane(sb + w * 1024);
+        pf_glds(kc, src + ((cp ^ q8_kswz(row)) << 4), dst);
+        pf_glds(vc, src + ((cp ^ q8_vswz(row)) << 4), dst + kQ8Img);
+        if (w < 2)
+            pf_glds_u16(sc, (unsigned)q8_min(kb * KB + lane, kend - 1) * 2u,
+                        __builtin_amdgcn_readfirstlane(sb + 2 * kQ8Img + w * (KB * 4)));
+    };
+    // the 64 fp32 q rows (32 KB) through stages 2 and 3, laid out and copied as in the fp16 kernel
+    char* qimg = smem + 2 * kQ8Stage;
+    {
+        const unsigned qb0 = lds0 + 2u * kQ8Stage;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int n = 8 * i + w, row = 2 * n + (lane >> 5), cp = lane & 31;
+            const unsigned src = (unsigned)q8_min(q_first + row, m_rows - 1) * (unsigned)ld * 4u + (unsigned)h * D * 4u +
+                                 (unsigned)((cp ^ (row & 31)) << 4);
+            pf_glds(qkv, src, __builtin_amdgcn_readfirstlane(qb0 + n * 1024));
+        }
+    }
+    for (int i = 0; i < 2; ++i)
+        if (i < nit) issue(i);
+
+    float m_run = -INFINITY, l_run = 0.f;  // this lane's query (column fr), log2 units
+    float v_ref = 5.9604644775390625e-8f;  // 2^-24, the least scale: wave-uniform power of two
+    f4 o[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) o[j] = f4{0.f, 0.f, 0.f, 0.f};
+    const int qpos = p0 + q_first + 16 * qt + fr;
+
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // q and blocks 0, 1 landed, for every wave
+    q8_sync();
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        const int row = 16 * qt + fr;
+        const float* qr = reinterpret_cast<const float*>(qimg + row * 512);
+        const f4 x0 = *reinterpret_cast<const f4*>(qr + 4 * ((8 * ks + 2 * fq) ^ (row & 31)));
+        const f4 x1 = *reinterpret_cast<const f4*>(qr + 4 * ((8 * ks + 2 * fq + 1) ^ (row & 31)));
+        const float v[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float x = q8_rounded(v[e] * qscale);
+            const _Float16 hi = (_Float16)x;
+            qa[0][ks][e] = hi;
+            if (P == 2) qa[P - 1][ks][e] = (_Float16)(x - (float)hi);
+        }
+    }
+    q8_sync();  // every wave read its q: stages 2, 3 are free for blocks 2, 3
+    const int qpos_max = p0 + q_first + 16 * qt + 15;  // the wave's last query
+    // this lane's addresses inside a stage: K row fr of tile 0 (chunk 2 ks + fq / 2, half fq % 2),
+    // the V row it supplies to the transposed read, and its 4 + 4 scales of each tile
+    const int krow = 32 * kp + fr;  // tile 1's row + 16 has the same swizzle
+    const int kofs = krow * D + 8 * (fq & 1), kch = (fq >> 1) ^ q8_kswz(krow);
+    const int vrow = 32 * kp + 16 * (fr >> 3) + 4 * fq + ((fr >> 1) & 3);
+    const int vofs = kQ8Img + vrow * D + 8 * (fr & 1), vch = q8_vswz(vrow);
+    const int sofs = 2 * kQ8Img + 4 * (32 * kp + 4 * fq);
+    for (int it = 0; it < nit; ++it) {
+        if ((it & 1) == 0) {  // blocks it, it + 1 landed; the stages of it - 2, it - 1 take the next pair
+            if (it > 0) {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                q8_sync();
+            }
+            if (it + 2 < nit) issue(it + 2);
+            if (it + 3 < nit) issue(it + 3);
+        }
+        const int kbase = (kb0 + it) * KB + 32 * kp;
+        if (kbase > qpos_max) continue;  // the half has no key visible to the wave's queries
+        const char* St = smem + (it % kQ8Stages) * kQ8Stage;
+        // S^T tile pair: s[j][e] = sum q k8 of key kbase + 16 j + 4 fq + e, then x the key's k scale
+        f4 s[2];
+        s[0] = s[1] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const h8 ak = q8_h8(*reinterpret_cast<const i2v*>(St + kofs + j * 16 * D + (((2 * ks) ^ kch) << 4)));
+#pragma unroll
+                for (int p = 0; p < P; ++p) s[j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ak, qa[p][ks], s[j], 0, 0, 0);
+            }
+        }
+        float sv[2][4];
+        float vmax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const u4v kd = *reinterpret_cast<const u4v*>(St + sofs + j * 64);
+            const u4v vd = *reinterpret_cast<const u4v*>(St + sofs + KB * 4 + j * 64);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                s[j][e] *= q8_scale(kd[e]);
+                sv[j][e] = q8_scale(vd[e]);
+                vmax = __builtin_fmaxf(vmax, sv[j][e]);  // a NaN scale is skipped here and reaches o[] through p
+            }
+        }
+        vmax = q8_xmax(vmax);  // the half's 32 keys: the same bits in every lane
+        // causal mask (key <= query position), only where the half reaches past the wave's first
+        // query or the keys' end (wave-uniform test); a select, after the scale
+        if (kbase + 31 > p0 + q_first + 16 * qt || kbase + 31 >= kend) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int key = kbase + 16 * j + 4 * fq + e;
+                    if (key > qpos || key >= kend) s[j][e] = -INFINITY;
+                }
+        }
+        // lazy online softmax (kTau = 8, p <= 256) as in the fp16 kernel; the V-scale reference is
+        // raised in the same, rarely taken, rescale pass
+        float mx = s[0][0];
+#pragma unroll
+        for (int e = 1; e < 8; ++e) mx = __builtin_fmaxf(mx, s[e >> 2][e & 3]);
+        mx = q8_xmax(mx);
+        constexpr float kTau = 8.f;
+        if (__builtin_amdgcn_ballot_w64(mx > m_run + kTau || vmax > v_ref) != 0) {
+            const float m_new = mx > m_run + kTau ? mx : m_run;
+            // 1 if unchanged, also for a lane whose query still has every key masked (-inf - -inf)
+            float alpha = m_new == m_run ? 1.f : __builtin_amdgcn_exp2f(m_run - m_new);
+            m_run = m_new;
+            l_run *= alpha;
+            if (vmax > v_ref) {  // up to the next power of two; old / new is exact
+                const float v_new = q8_float((q8_bits(vmax) + 0x007FFFFFu) & 0x7F800000u);
+                alpha *= v_ref * q8_float((254u << 23) - q8_bits(v_new));
+                v_ref = v_new;
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j] *= alpha;
+        }
+        const float m_use = m_run == -INFINITY ? 0.f : m_run;  // every key so far masked: p = 0
+        const float v_inv = q8_float((261u << 23) - q8_bits(v_ref));  // 128 / v_ref
+        float ps = 0.f;
+        h8 pb[P];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float pv = __builtin_amdgcn_exp2f(s[j][e] - m_use);
+                ps += pv;  // l takes the unscaled sum
+                const float x = q8_rounded(s[j][e] == -INFINITY ? 0.f : pv * (sv[j][e] * v_inv));
+                const _Float16 hi = (_Float16)x;
+                pb[0][4 * j + e] = hi;
+                if (P == 2) pb[P - 1][4 * j + e] = (_Float16)(x - (float)hi);
+            }
+        ps = q8_xsum(ps);
+        l_run += ps;
+
+        // O^T += V^T P^T over the half's 32 keys: one transposed read per 16 dims
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) {
+            const h8 av = q8_h8(__builtin_amdgcn_ds_read_tr8_b64_v2i32(
+                (__attribute__((address_space(3))) i2v*)(St + vofs + ((dt ^ vch) << 4))));
+#pragma unroll
+            for (int p = 0; p < P; ++p) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(av, pb[p], o[dt], 0, 0, 0);
+        }
+    }
+    {  // back to the fp16 kernel's units: sum p v8 s_v
+        const float back = v_ref * 0.0078125f;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] *= back;
+    }
+
+    // epilogue, as the fp16 kernel's, with the halves combined in place. o[dt][e] =
+    // O[query 16 qt + fr][dim 16 dt + 4 fq + e] of this key half
+    constexpr int kIs = D + 4;
+    q8_sync();  // every wave is done with the stages (no copy is in flight)
+    float* img = reinterpret_cast<float*>(smem);  // half 1's O rows [64][kIs], then the combined rows
+    float* ml1 = img + QM * kIs;                  // half 1's m, l [2][64]
+    const int lr = 16 * qt + fr;
+    if (kp == 1) {
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) *reinterpret_cast<f4*>(img + lr * kIs + 16 * dt + 4 * fq) = o[dt];
+        if (fq == 0) {
+            ml1[lr] = m_run;
+            ml1[QM + lr] = l_run;
+        }
+    }
+    q8_sync();
+    if (kp == 0) {
+        const float m1 = ml1[lr], l1 = ml1[QM + lr];
+        const float M = __builtin_fmaxf(m_run, m1);
+        const float M_use = M == -INFINITY ? 0.f : M;
+        const float a0 = __builtin_amdgcn_exp2f(m_run - M_use), a1 = __builtin_amdgcn_exp2f(m1 - M_use);
+        const float L = l_run * a0 + l1 * a1;
+        const float sn = nch > 1 ? 1.f : 1.0f / L;
+        const float s0 = a0 * sn, s1 = a1 * sn;
+#pragma unroll
+        for (int dt = 0; dt < 8; ++dt) {  // the lane that reads an element is the one that rewrites it
+            f4* e = reinterpret_cast<f4*>(img + lr * kIs + 16 * dt + 4 * fq);
+            *e = o[dt] * s0 + *e * s1;
+        }
+        if (nch > 1 && fq == 0) {
+            float* part = ws + ((size_t)(h * nqb + qb) * maxc + chunk) * kPartFloats;
+            part[QM * D + lr] = M;
+            part[QM * D + QM + lr] = L;
+        }
+    }
+    q8_sync();
+    if (nch > 1) {  // partial: unnormalised O rows of this chunk (m, l written above)
+        float* part = ws + ((size_t)(h * nqb + qb) * maxc + chunk) * kPartFloats;
+#pragma unroll
+        for (int i = 0; i < QM * D / 4 / kTrThreads; ++i) {
+            const int f = i * kTrThreads + t, rr = f >> 5, c4 = f & 31;
+            reinterpret_cast<f4*>(part)[f] = *reinterpret_cast<const f4*>(img + rr * kIs + 4 * c4);
+        }
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < QM * D / 8 / kTrThreads; ++i) {
+        const int f = i * kTrThreads + t, rr = f >> 4, c8 = f & 15;
+        const int row = q_first + rr;
+        if (row >= m_rows) continue;
+        const f4 x0 = *reinterpret_cast<const f4*>(img + rr * kIs + 8 * c8);
+        const f4 x1 = *reinterpret_cast<const f4*>(img + rr * kIs + 8 * c8 + 4);
+        const size_t idx = (size_t)row * ldo + (size_t)h * D + 8 * c8;
+        if (out_hi) {
+            const float v[8] = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
+            h8 hv, lv;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                hv[e] = (_Float16)v[e];
+                lv[e] = (_Float16)(v[e] - (float)hv[e]);
+            }
+            *reinterpret_cast<h8*>(out_hi + idx) = hv;
+            if (out_lo) *reinterpret_cast<h8*>(out_lo + idx) = lv;
+        } else {
+            *reinterpret_cast<f4*>(out + idx) = x0;
+            *reinterpret_cast<f4*>(out + idx + 4) = x1;
+        }
+    }
+}
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma clang attribute pop
+#endif
+
 // grid (nqb, heads), block 256: the chunks of a split query block, combined in chunk
 // order: M = max m_c, L = sum l_c e^(m_c - M), O = sum O_c e^(m_c - M) / L. Four passes
 // of 16 rows; thread t: row 16 pass + t / 16, dims 8 (t % 16) .. + 8, so 16 lanes cover a
@@ -762,7 +1153,10 @@ int prefill_attn_check(const PrefillAttnArgs& a) {
     LLMI_REQUIRE(a.mfma_planes == 0 || ((a.mfma_planes == 1 || a.mfma_planes == 2) && a.cache_dtype == LLMI_F16 &&
                                         (a.out || a.out_hi)),
                  "prefill attention: the MFMA form needs the fp16 cache, 1 or 2 planes and an output");
-    LLMI_REQUIRE(a.mfma_planes != 0 || a.out, "prefill attention: null output");
+    LLMI_REQUIRE(a.mfma_planes != 0 || a.q8_planes != 0 || a.out, "prefill attention: null output");
+    LLMI_REQUIRE(a.q8_planes == 0 || ((a.q8_planes == 1 || a.q8_planes == 2) && a.cache_dtype == LLMI_I8 &&
+                                      a.mfma_planes == 0 && (a.out || a.out_hi) && !a.out_lo8),
+                 "prefill attention: the int8 MFMA form needs the int8 cache, 1 or 2 planes, an output and no e4m3 lo");
     LLMI_REQUIRE(a.cache_dtype == LLMI_F16 || a.cache_dtype == LLMI_F32 || a.cache_dtype == LLMI_I8,
                  "prefill attention: cache dtype must be f16, f32 or i8");
     LLMI_REQUIRE(a.cache_dtype != LLMI_I8 || (a.k_scale && a.v_scale && (uintptr_t)a.k_cache % 4 == 0 &&
@@ -777,7 +1171,7 @@ int prefill_attn_check(const PrefillAttnArgs& a) {
 int prefill_attn_plan(const PrefillAttnArgs& a, PrefillAttnPlan* p) {
     LLMI_REQUIRE(p != nullptr, "prefill attention plan: null output");
     LLMI_TRY(prefill_attn_check(a));
-    if (!a.mfma_planes) {
+    if (!a.mfma_planes && !a.q8_planes) {
         p->cb = 0;
         p->maxc = 1;
         p->grid = ((a.m + QB - 1) / QB) * a.heads;
@@ -825,6 +1219,21 @@ int prefill_attn_plan(const PrefillAttnArgs& a, PrefillAttnPlan* p) {
     return LLMI_OK;
 }
 
+// the split-key partials of either MFMA form, combined
+static void prefill_merge_launch(const PrefillAttnArgs& a, const PrefillAttnPlan& plan, hipStream_t s) {
+    const int nqb = (a.m + QM - 1) / QM;
+#define PF_MERGE(C)                                                                                             \
+    hipLaunchKernelGGL(attn_prefill_merge_kernel<C>, dim3(nqb, a.heads), dim3(kThreads), 0, s, a.split_ws, plan.maxc, \
+                       plan.cb, a.m, a.p0, a.out, a.out_hi, a.out_lo, a.heads * D, a.out_lo8)
+    if (plan.merge_slots == 2)
+        PF_MERGE(2);
+    else if (plan.merge_slots == 4)
+        PF_MERGE(4);
+    else
+        PF_MERGE(8);
+#undef PF_MERGE
+}
+
 int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
     PrefillAttnPlan plan;
     LLMI_TRY(prefill_attn_plan(a, &plan));
@@ -835,7 +1244,6 @@ int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
                            a.kv_heads, a.rope_tab, (__half*)a.k_cache, (__half*)a.v_cache, a.max_seq, (__half*)nullptr,
                            (__half*)nullptr);
         if (a.mfma_planes) {
-            const int nqb = (a.m + QM - 1) / QM;
             const int cb = plan.cb, maxc = plan.maxc;
             const dim3 gm(plan.grid);
             unsigned long long* st = g_pf_stamps.load(std::memory_order_relaxed);
@@ -848,18 +1256,7 @@ int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
             else
                 PF_ATTN(1);
 #undef PF_ATTN
-            if (maxc > 1) {
-#define PF_MERGE(C)                                                                                              \
-    hipLaunchKernelGGL(attn_prefill_merge_kernel<C>, dim3(nqb, a.heads), dim3(kThreads), 0, s, a.split_ws, maxc, cb, \
-                       a.m, a.p0, a.out, a.out_hi, a.out_lo, a.heads * D, a.out_lo8)
-                if (plan.merge_slots == 2)
-                    PF_MERGE(2);
-                else if (plan.merge_slots == 4)
-                    PF_MERGE(4);
-                else
-                    PF_MERGE(8);
-#undef PF_MERGE
-            }
+            if (maxc > 1) prefill_merge_launch(a, plan, s);
         } else {
             hipLaunchKernelGGL(attn_prefill_kernel<__half>, ga, dim3(kThreads), 0, s, a.qkv, ld, a.m, a.p0, a.heads,
                                a.kv_heads, (const __half*)a.k_cache, (const __half*)a.v_cache, a.max_seq, a.out,
@@ -869,9 +1266,24 @@ int prefill_attn_launch(const PrefillAttnArgs& a, hipStream_t s) {
         hipLaunchKernelGGL(rope_kv_prefill_kernel<int8_t>, dim3(a.m), dim3(pf_rope_threads()), 0, s, a.qkv, a.qkv2, ld,
                            a.p0, a.heads, a.kv_heads, a.rope_tab, (int8_t*)a.k_cache, (int8_t*)a.v_cache, a.max_seq,
                            a.k_scale, a.v_scale);
+        if (a.q8_planes) {
+            const dim3 gm(plan.grid);
+#define PF_ATTN(PL)                                                                                               \
+    hipLaunchKernelGGL(attn_prefill_q8_kernel<PL>, gm, dim3(kTrThreads), 0, s, a.qkv, ld, a.m, a.p0, a.heads,     \
+                       a.kv_heads, (const int8_t*)a.k_cache, (const int8_t*)a.v_cache, (const __half*)a.k_scale,  \
+                       (const __half*)a.v_scale, a.max_seq, a.out, a.out_hi, a.out_lo, a.heads * D, plan.cb,      \
+                       a.split_ws, plan.maxc)
+            if (a.q8_planes == 2)
+                PF_ATTN(2);
+            else
+                PF_ATTN(1);
+#undef PF_ATTN
+            if (plan.maxc > 1) prefill_merge_launch(a, plan, s);
+        } else {
         hipLaunchKernelGGL(attn_prefill_kernel<int8_t>, ga, dim3(kThreads), 0, s, a.qkv, ld, a.m, a.p0, a.heads,
                            a.kv_heads, (const int8_t*)a.k_cache, (const int8_t*)a.v_cache, a.max_seq, a.out,
                            a.heads * D, (const __half*)a.k_scale, (const __half*)a.v_scale);
+        }
     } else {
         hipLaunchKernelGGL(rope_kv_prefill_kernel<float>, dim3(a.m), dim3(pf_rope_threads()), 0, s, a.qkv, a.qkv2, ld, a.p0, a.heads,
                            a.kv_heads, a.rope_tab, (float*)a.k_cache, (float*)a.v_cache, a.max_seq, (__half*)nullptr,

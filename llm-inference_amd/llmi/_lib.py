@@ -79,7 +79,7 @@ class DebugPrefillAttnArgs(C.Structure):
                 ("rope_tab", C.c_void_p), ("out", C.c_void_p), ("mfma_planes", C.c_int),
                 ("out_hi", C.c_void_p), ("out_lo", C.c_void_p), ("out_lo8", C.c_int),
                 ("split_ws", C.c_void_p), ("split_ws_floats", C.c_size_t), ("chunk_blocks", C.c_int),
-                ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
+                ("k_scale", C.c_void_p), ("v_scale", C.c_void_p), ("q8_planes", C.c_int)]
 
 
 class DebugGemmArgs(C.Structure):

@@ -18,7 +18,8 @@ appended to --out as a list:
            engine with the fused q/k/v + attention launch and with qkv_attn 0, the int8 engine
            (which always takes the two launches)
   batch    Batch of 8 slots, aggregate tokens/s over positions 1792 .. 2047
-  prefill  one 512-row prefill in ms: int8 KV against fp32 KV (both run the scalar attention)
+  prefill  one 512-row prefill in ms: int8 KV (the int8 MFMA attention) against fp32 KV (the scalar one)
+  prefill_long  (asked for by name) prefill(512) at p0 = 0, the 512-row chunk at p0 = 1536 and 2047 rows
   depth    32 layers: the fp32-KV engine's 8 prompt ids + 16 greedy tokens are fed to every engine
            (one sequence for all); final logits rel-L2 of the int8-KV and the fp16-KV engine
            against the fp32-KV engine, and how many tokens of each engine's own greedy run agree
@@ -159,6 +160,33 @@ def part_prefill(kvs, passes, tag, rows=512):
         e.close()
 
 
+def part_prefill_long(kvs, passes, tag):
+    """int8 KV beside fp16 KV: prefill(512) at p0 = 0, the 512-row chunk at p0 = 1536, 2047 rows."""
+    engs = {kv: engine(kv, max_seq=2112) for kv in kvs}
+    prompt = synth_prompt(3, 2049, 32000)
+
+    def run(e, before, rows):
+        e.set_prompt(prompt)
+        if before:
+            e.prefill(before)
+        e.sync()
+        t0 = time.perf_counter()
+        e.prefill(rows)
+        e.sync()
+        return time.perf_counter() - t0
+    shapes = [(0, 512), (1536, 512), (0, 2047)]
+    for e in engs.values():
+        for before, rows in shapes:
+            run(e, before, rows)
+    for p in range(passes):
+        for before, rows in shapes:
+            for kv, e in engs.items():
+                emit(part="prefill_long", tag=tag, kv=kv, p0=before, rows=rows, pass_=p,
+                     ms=round(run(e, before, rows) * 1e3, 3))
+    for e in engs.values():
+        e.close()
+
+
 def part_depth(kvs, tag, n_prompt=8, n_new=16):
     prompt = synth_prompt(0, n_prompt, 32000)
     res = {}
@@ -199,6 +227,8 @@ def main():
         part_batch(kvs, a.passes, a.tag)
     if "prefill" in parts:
         part_prefill(kvs, a.passes, a.tag)
+    if "prefill_long" in parts:
+        part_prefill_long(kvs, a.passes, a.tag)
     if "depth" in parts:
         part_depth(kvs, a.tag)
     # medians per (part, kv, form / ctx)
