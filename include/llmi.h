@@ -395,6 +395,33 @@ typedef struct llmi_debug_gemm1_args {
 int llmi_debug_gemm1(const llmi_debug_gemm1_args* args, llmi_stream_t stream);
 int llmi_debug_gemm1_plan(const llmi_debug_gemm1_args* args, int* bm, int* grid);
 
+/* llmi_debug_gemm_w8: one launch of the int8-weight prefill GEMM (gemm_w8.hip, the GEMM an int8
+ * engine's prefill runs), Y (op)= s[n] * sum_p A_p q^T, its argument block (GemmW8Args) filled
+ * field for field and handed to the production launcher (test-only: no engine or operator path
+ * calls it). a_hi (, a_lo): fp16 planes [m, lda], planes 1 or 2; w: int8 [n, k] row-major;
+ * scales: one fp16 per row of w. epi: 0 store (y [m, ldy] fp32), 5 slab (slab [ksplit][m][ldy]:
+ * slice s holds the scaled sum over its K range alone), 2 gate_up (w = [gate; up] rows,
+ * n = 2 x inter, pair_off = n / 2: silu(s_g gate) * (s_u up) into y [m, ldy] fp32 or, with y_hi
+ * (, y_lo), as fp16 planes). k / ksplit must be a multiple of 128, n of 128 (gate_up: n / 2 of
+ * 64): LLMI_EUNSUPPORTED otherwise; a null operand, scale or output: LLMI_EINVAL. Nothing is
+ * launched on a refused call. The caller owns every buffer. */
+typedef struct llmi_debug_gemm_w8_args {
+    const void* a_hi;
+    const void* a_lo;
+    int planes, lda;
+    const void* w;
+    const void* scales;
+    int m, n, k;
+    int epi, pair_off;
+    float* y;
+    void* y_hi;
+    void* y_lo;
+    int ldy;
+    int ksplit;
+    float* slab;
+} llmi_debug_gemm_w8_args;
+int llmi_debug_gemm_w8(const llmi_debug_gemm_w8_args* args, llmi_stream_t stream);
+
 /* llmi_debug_rows_split: the prefill GEMMs' activation producer. Rows of x [m, ldx] (k used):
  * with slab [ksplit][m][k] (ldx == k) x += slice 0 + slice 1 + ... in that order, written
  * back; then optional RMSNorm (gamma [k] of g_dtype f16 / f32; NULL: none); then fp16 planes
@@ -1129,7 +1156,11 @@ int llmi_engine_xchg_loopback(llmi_engine* e);
  * handed over as tagged 8-byte granules; bitwise the two launches), 0 as two. "qa_o": 1 adds the
  * o_proj to that launch (fp16 MHA, single rank; default 0, measured slower). "qa_grid" (workgroups
  * of the fused launch's GEMV part, 0 = every resident slot), "qa_order" (1 head-major rows and
- * attention blocks, default), "qa_poll" (1 poll every granule from the start): A/B only. */
+ * attention blocks, default), "qa_poll" (1 poll every granule from the start): A/B only.
+ * "w8_gemm": 1 (default) runs an int8 (W8A16) engine's prefill layers on the LDS-DMA MFMA GEMM for
+ * int8 weights (gemm_w8.hip: fp16 planes handed from launch to launch, split-K slabs, the MFMA
+ * prefill attention for fp16 and int8 caches) where every projection's K is a multiple of 128;
+ * 0 keeps them on the first-generation GEMM (gemm.hip). A batch slot follows slot 0's setting. */
 int llmi_engine_set_option(llmi_engine* e, const char* name, int value);
 int llmi_engine_set_exchange(llmi_engine* e, int mode);
 /* Diagnostics: kernels launched by llmi_engine_time_kernel (and graphs built

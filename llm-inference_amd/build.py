@@ -60,8 +60,14 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
+# units compiled without the packed fp32 VALU forms (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32)
+NO_PK_F32 = {"gemm_w8.hip"}
+_NO_PK_F32_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+
+
 def _compile(src, obj):
-    cmd = [HIPCC, *CFLAGS, "-c", src, "-o", obj]
+    extra = _NO_PK_F32_FLAGS if os.path.basename(src) in NO_PK_F32 else []
+    cmd = [HIPCC, *CFLAGS, *extra, "-c", src, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"compile failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")

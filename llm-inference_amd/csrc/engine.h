@@ -297,6 +297,10 @@ struct Engine {
     static constexpr int kPfSplit = 2;   // o_proj (gemm2) K slices
     static constexpr int kPfDown = 8;    // down (gemm3) K slices
     static constexpr int kPfSlabs = 8;
+    // int8 weights: the layers on prefill_layer_gemm2 with gemm_w8.hip's GEMMs (option "w8_gemm",
+    // default 1) where w8_prefill_supported(); 0 keeps them on gemm.hip
+    bool w8_gemm = true;
+    bool w8_prefill_supported() const;
     // split mode 3: e4m3 copies of the prefill GEMM weights (W * 2^exp, gemm3.hip), made on first use
     struct W8Layer {
         void *qkv = nullptr, *o = nullptr, *gu = nullptr, *down = nullptr;

@@ -405,8 +405,11 @@ int Engine::set_option(const std::string& name, int value) {
         qkv_attn_set_order(value);
     } else if (name == "qa_poll") {
         qkv_attn_set_poll(value);
+    } else if (name == "w8_gemm") {
+        LLMI_REQUIRE(value == 0 || value == 1, "set_option w8_gemm: 1 int8 prefill on gemm_w8 (default), 0 on gemm");
+        w8_gemm = value == 1;
     } else {
-        LLMI_REQUIRE(false, "set_option: unknown option (kpar, qkv_attn, qa_o, qa_grid, qa_order, qa_poll)");
+        LLMI_REQUIRE(false, "set_option: unknown option (kpar, qkv_attn, qa_o, qa_grid, qa_order, qa_poll, w8_gemm)");
     }
     return invalidate();
 }

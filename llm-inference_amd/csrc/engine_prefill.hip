@@ -69,6 +69,26 @@ int Engine::alloc_w8() {
     return LLMI_OK;
 }
 
+// int8 weights on prefill_layer_gemm2: g's launch on gemm_w8.hip with the weight's row scales
+// (g.epi EPI_STORE, EPI_SLAB or EPI_SILU_MUL; no head-major blocks, no fp8 lo plane)
+static int w8_launch(const Gemm2Args& g, const __half* scales, hipStream_t s) {
+    GemmW8Args a;
+    a.a[0] = g.a[0]; a.a[1] = g.a[1]; a.planes = g.planes; a.lda = g.lda;
+    a.w = g.w; a.scales = scales; a.m = g.m; a.n = g.n; a.k = g.k;
+    a.epi = g.epi; a.pair_off = g.pair_off;
+    a.y = g.y; a.y_hi = g.y_hi; a.y_lo = g.y_lo; a.ldy = g.ldy;
+    a.ksplit = g.ksplit; a.slab = g.slab;
+    return gemm_w8_launch(a, s);
+}
+// K slices of an int8 o_proj / down GEMM: kPfSplit where each slice keeps whole B stages
+static int w8_slices(int k) { return k % (Engine::kPfSplit * 128) == 0 ? Engine::kPfSplit : 1; }
+bool Engine::w8_prefill_supported() const {
+    return wdt == LLMI_I8 && gemm_w8_supported(ql + 2 * kvrows, c.hidden, EPI_STORE, 1) &&
+           gemm_w8_supported(c.hidden, ql, EPI_SLAB, w8_slices(ql)) &&
+           gemm_w8_supported(2 * il, c.hidden, EPI_SILU_MUL, 1) &&
+           gemm_w8_supported(c.hidden, il, EPI_SLAB, w8_slices(il)) && c.head_dim % 64 == 0;
+}
+
 // rope + KV write + causal attention of rows [p0, p0 + m) of layer l: the fields both prefill
 // paths share
 PrefillAttnArgs Engine::prefill_attn_args(int l, int m, int p0) const {
@@ -84,10 +104,12 @@ PrefillAttnArgs Engine::prefill_attn_args(int l, int m, int p0) const {
 
 // One prefill layer on the LDS-DMA GEMM (gemm2.hip): RMSNorm + split into fp16
 // planes, q/k/v GEMM, rope + KV write + causal attention, split, o_proj (+residual),
-// RMSNorm + split, gate_up GEMM writing silu(g) * u as planes, down (+residual).
+// RMSNorm + split, gate_up GEMM writing silu(g) * u as planes, down (+residual). int8 weights:
+// the same launches with every GEMM on gemm_w8.hip (128 x 128 tiles; no gemm3 form).
 int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     const Layer& L = layers[l];
     const int H = c.hidden;
+    const bool i8 = wdt == LLMI_I8;
     // split 3: the lo planes are e4m3 bytes against the e4m3 weight copies (gemm3.hip)
     const bool f8 = split == 3;
     const W8Layer* W8 = f8 ? &w8l[l] : nullptr;
@@ -101,13 +123,13 @@ int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     g.lda = H; g.w = L.qkv; g.n = ql + 2 * kvrows; g.k = H;
     g.ldy = g.n;
     if (f8) { g.w8 = W8->qkv; g.w8_exp = W8->qkv_e; }
-    const bool qkv3 = gemm3_supported(g.n, H, EPI_SLAB, 2);
+    const bool qkv3 = !i8 && gemm3_supported(g.n, H, EPI_SLAB, 2);
     if (qkv3) {  // two K slices (96 tiles alone would leave most CUs idle)
         g.epi = EPI_SLAB; g.ksplit = 2; g.slab = pf_qkv;
         LLMI_TRY(gemm3_launch(g, stream));
     } else {
         g.epi = EPI_STORE; g.y = pf_qkv;
-        LLMI_TRY(gemm2_launch(g, stream));
+        LLMI_TRY(i8 ? w8_launch(g, L.qkv_s, stream) : gemm2_launch(g, stream));
     }
     // rope (+ the second qkv slice) + kv write + causal attention
     PrefillAttnArgs pa = prefill_attn_args(l, m, p0);
@@ -126,14 +148,14 @@ int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     // split-K into slabs (128 tiles alone would leave half the CUs idle); the next
     // rows_split adds the slices into x in slice order (deterministic). The fp8 lo
     // pass is gemm3's: 8 slices of 256 x 256 tiles (256 workgroups)
-    int so = (ql % (kPfSplit * 64)) == 0 ? kPfSplit : 1;
+    int so = i8 ? w8_slices(ql) : (ql % (kPfSplit * 64)) == 0 ? kPfSplit : 1;
     g.lda = ql; g.w = L.o; g.w_kblock = 0; g.n = H; g.k = ql;
     g.epi = EPI_SLAB; g.ksplit = so; g.slab = pf_slab; g.y = pf_x; g.ldy = H;
     if (f8) {
         so = kPfDown; g.ksplit = so; g.w8 = W8->o; g.w8_exp = W8->o_e;
         LLMI_TRY(gemm3_launch(g, stream));
     } else {  // (the fp16 o_proj on gemm3's 8 K slices measured 0.1 ms slower a 7B prefill, r07l)
-        LLMI_TRY(gemm2_launch(g, stream));
+        LLMI_TRY(i8 ? w8_launch(g, L.o_s, stream) : gemm2_launch(g, stream));
     }
     g.w_kblock = 0;
     // (o slices into x) + rmsnorm + gate_up + silu * up -> planes of the down GEMM's input
@@ -148,11 +170,12 @@ int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     g.sk_slab = nullptr; g.sk_flags = nullptr; g.sk_grid = 0;
     // the whole K work of gate_up's 172 tiles spread evenly over every CU (gemm3 stream-K),
     // the fp8 lo pass included
-    if (gemm3_supported(g.n, H, EPI_SILU_MUL, 1)) {
+    const bool gu3 = !i8 && gemm3_supported(g.n, H, EPI_SILU_MUL, 1);
+    if (gu3) {
         g.err = &st->error;
         (void)gemm3_sk_attach(g, stream);
     }
-    LLMI_TRY(gemm3_supported(g.n, H, EPI_SILU_MUL, 1) ? gemm3_launch(g, stream) : gemm2_launch(g, stream));
+    LLMI_TRY(gu3 ? gemm3_launch(g, stream) : i8 ? w8_launch(g, L.gu_s, stream) : gemm2_launch(g, stream));
     // down + residual: K slices into slabs (gemm3: 8 uneven slices, 256 workgroups)
     g.sk_slab = nullptr; g.sk_flags = nullptr; g.sk_grid = 0;
     g.a[0] = pf_act_h(); g.a[1] = split >= 2 ? pf_act_l() : nullptr;
@@ -160,7 +183,10 @@ int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     if (f8) { g.w8 = W8->down; g.w8_exp = W8->down_e; }
     g.epi = EPI_SLAB; g.pair_off = 0; g.y = pf_x; g.y_hi = g.y_lo = nullptr; g.ldy = H; g.slab = pf_slab;
     int sd;
-    if (gemm3_supported(H, il, EPI_SLAB, kPfDown)) {
+    if (i8) {
+        sd = w8_slices(il); g.ksplit = sd;
+        LLMI_TRY(w8_launch(g, L.down_s, stream));
+    } else if (gemm3_supported(H, il, EPI_SLAB, kPfDown)) {
         sd = kPfDown; g.ksplit = sd;
         LLMI_TRY(gemm3_launch(g, stream));
     } else {
@@ -261,7 +287,11 @@ int Engine::prefill(int n, int split, bool scored) {
     const bool use_gemm2 = wdt == LLMI_F16 && gemm2_supported(ql + 2 * kvrows, c.hidden, EPI_STORE) &&
                            gemm2_supported(c.hidden, ql, EPI_ADD) && gemm2_supported(2 * il, c.hidden, EPI_SILU_MUL) &&
                            gemm2_supported(c.hidden, il, EPI_ADD) && c.head_dim % 64 == 0;
+    // int8 weights: the same layer function on gemm_w8.hip's GEMMs (option "w8_gemm" 0: gemm.hip, below)
+    const bool use_w8 = (pf_from ? pf_from : this)->w8_gemm && w8_prefill_supported();
+    const bool layers_gemm2 = use_gemm2 || use_w8;
     // no GEMM form for the lm_head shape: decode steps, which score every row themselves
+    // (an int8 engine's fp16 lm_head stays on gemm.hip with either layer route)
     if (scored && !head_gemm_supported(use_gemm2)) return decode(n, 1);
     if (split == 3 && !(use_gemm2 && lo8_supported())) split = 2;  // shapes without the fp8 lo pass: exact planes
     LLMI_TRY(prefill_scratch(split, scored));
@@ -271,7 +301,7 @@ int Engine::prefill(int n, int split, bool scored) {
         LLMI_TRY(embedding_launch(prompt + p0, m, embed, edt, c.vocab, H, pf_x, stream));
         for (int l = 0; l < c.layers; ++l) {
             const Layer& L = layers[l];
-            if (use_gemm2) {
+            if (layers_gemm2) {
                 LLMI_TRY(prefill_layer_gemm2(l, m, p0, split));
                 continue;
             }

@@ -214,6 +214,29 @@ struct Gemm2Args {
     int sk_pmax = 0;               // set by gemm3_launch; bits 8+: fault injection (llmi_debug_stream_k:
                                    // 1 never publish, 2 publish 2.5 s late)
 };
+// The same GEMM for int8 weights with one fp16 scale per output row (gemm_w8.hip):
+// Y (op)= s[n] * sum_p sum_k A_p[m, k] q[n, k], the scale applied in fp32 in the epilogue.
+struct GemmW8Args {
+    const _Float16* a[2] = {nullptr, nullptr};  // [m, lda] planes (lda >= k)
+    int planes = 2;
+    int lda = 0;
+    const void* w = nullptr;          // [n, k] int8, row-major
+    const __half* scales = nullptr;   // [n]
+    int m = 0, n = 0, k = 0;
+    int epi = EPI_STORE;              // EPI_STORE, EPI_SLAB, EPI_SILU_MUL
+    int pair_off = 0;
+    float* y = nullptr;               // [m, ldy] fp32
+    _Float16* y_hi = nullptr;         // EPI_SILU_MUL: write the result as fp16 planes instead
+    _Float16* y_lo = nullptr;
+    int ldy = 0;
+    int ksplit = 1;                   // EPI_SLAB: K slices (K / ksplit a multiple of 128)
+    float* slab = nullptr;            // EPI_SLAB: [ksplit][m][ldy] partial sums, each scaled
+    int n_tiles = 0;                  // set by gemm_w8_launch
+};
+// N as gemm2_supported; K / ksplit (ksplit counts under EPI_SLAB only) a multiple of 128
+bool gemm_w8_supported(int n, int k, int epi, int ksplit);
+// LLMI_EUNSUPPORTED, nothing launched, for a shape or epilogue gemm_w8_supported refuses
+int gemm_w8_launch(GemmW8Args a, hipStream_t s);
 constexpr int kSkCtlWords = 64;    // stream-K control words ahead of the flags (256 B)
 // the next `launches` stream-K launches run with sk_test = mode (llmi_debug_stream_k)
 void gemm3_sk_debug(int mode, int launches);
