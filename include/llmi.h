@@ -422,6 +422,35 @@ typedef struct llmi_debug_gemm_w8_args {
 } llmi_debug_gemm_w8_args;
 int llmi_debug_gemm_w8(const llmi_debug_gemm_w8_args* args, llmi_stream_t stream);
 
+/* llmi_debug_gemm_w4: one launch of the int4-weight prefill GEMM (gemm_w4.hip, the GEMM an int4
+ * engine's prefill runs under option "w4_gemm"), Y (op)= sum_g s[n, g] * sum_{k in g} sum_p A_p q^T
+ * with each group's fp32 sum scaled in fp32, its argument block (GemmW4Args) filled field for
+ * field and handed to the production launcher (test-only: no engine or operator path calls it).
+ * a_hi (, a_lo): fp16 planes [m, lda], planes 1 or 2; w: the LLMI_I4 bytes [n, k / 2] (nibble
+ * q + 8, the even column low; nibble 0 is -8); scales: fp16 [n][k / 128] (llmi_quantize_groups_i4).
+ * epi: 0 store (y [m, ldy] fp32), 5 slab (slab [ksplit][m][ldy]: slice s holds the scaled sum over
+ * its own groups alone), 2 gate_up (w = [gate; up] rows, n = 2 x inter, pair_off = n / 2:
+ * silu(gate) * up into y [m, ldy] fp32 or, with y_hi (, y_lo), as fp16 planes). k / ksplit must be
+ * a multiple of 128 (at most 24576), n of 128 (gate_up: n / 2 of 64): LLMI_EUNSUPPORTED otherwise;
+ * a null operand, scale or output: LLMI_EINVAL. Nothing is launched on a refused call. The caller
+ * owns every buffer. */
+typedef struct llmi_debug_gemm_w4_args {
+    const void* a_hi;
+    const void* a_lo;
+    int planes, lda;
+    const void* w;
+    const void* scales;
+    int m, n, k;
+    int epi, pair_off;
+    float* y;
+    void* y_hi;
+    void* y_lo;
+    int ldy;
+    int ksplit;
+    float* slab;
+} llmi_debug_gemm_w4_args;
+int llmi_debug_gemm_w4(const llmi_debug_gemm_w4_args* args, llmi_stream_t stream);
+
 /* llmi_debug_rows_split: the prefill GEMMs' activation producer. Rows of x [m, ldx] (k used):
  * with slab [ksplit][m][k] (ldx == k) x += slice 0 + slice 1 + ... in that order, written
  * back; then optional RMSNorm (gamma [k] of g_dtype f16 / f32; NULL: none); then fp16 planes
@@ -1160,7 +1189,13 @@ int llmi_engine_xchg_loopback(llmi_engine* e);
  * "w8_gemm": 1 (default) runs an int8 (W8A16) engine's prefill layers on the LDS-DMA MFMA GEMM for
  * int8 weights (gemm_w8.hip: fp16 planes handed from launch to launch, split-K slabs, the MFMA
  * prefill attention for fp16 and int8 caches) where every projection's K is a multiple of 128;
- * 0 keeps them on the first-generation GEMM (gemm.hip). A batch slot follows slot 0's setting. */
+ * 0 keeps them on the first-generation GEMM (gemm.hip). A batch slot follows slot 0's setting.
+ * "w4_gemm": 1 gives an int4 (W4A16) engine a prompt pass: the same prefill layers with q/k/v,
+ * gate_up and down on the MFMA GEMM for 4-bit group-quantised weights (gemm_w4.hip, reading the
+ * decode GEMVs' nibbles and group scales in place) and the int8 W_o on gemm_w8.hip, for the
+ * prefill, the scored prefill and a draft engine's catch-up; a shape those GEMMs refuse (rows not
+ * in multiples of 128, head_dim not a multiple of 64) is LLMI_EUNSUPPORTED. 0 (default): an int4
+ * engine refuses prefill and runs its prompt as decode steps. */
 int llmi_engine_set_option(llmi_engine* e, const char* name, int value);
 int llmi_engine_set_exchange(llmi_engine* e, int mode);
 /* Diagnostics: kernels launched by llmi_engine_time_kernel (and graphs built

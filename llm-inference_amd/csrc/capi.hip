@@ -383,6 +383,20 @@ int llmi_debug_gemm_w8(const llmi_debug_gemm_w8_args* args, llmi_stream_t stream
     return gemm_w8_launch(a, STREAM(stream));  // every check first: nothing is launched on a refused call
 }
 
+int llmi_debug_gemm_w4(const llmi_debug_gemm_w4_args* args, llmi_stream_t stream) {
+    LLMI_REQUIRE(args != nullptr, "debug_gemm_w4: null arguments");
+    const llmi_debug_gemm_w4_args& d = *args;
+    GemmW4Args a;
+    a.a[0] = static_cast<const _Float16*>(d.a_hi); a.a[1] = static_cast<const _Float16*>(d.a_lo);
+    a.planes = d.planes; a.lda = d.lda;
+    a.w = d.w; a.scales = static_cast<const __half*>(d.scales);
+    a.m = d.m; a.n = d.n; a.k = d.k;
+    a.epi = d.epi; a.pair_off = d.pair_off;
+    a.y = d.y; a.y_hi = static_cast<_Float16*>(d.y_hi); a.y_lo = static_cast<_Float16*>(d.y_lo); a.ldy = d.ldy;
+    a.ksplit = d.ksplit; a.slab = d.slab;
+    return gemm_w4_launch(a, STREAM(stream));  // every check first: nothing is launched on a refused call
+}
+
 int llmi_debug_rows_split(float* x, int ldx, int m, int k, const void* gamma, int g_dtype, float eps, void* hi,
                           void* lo, int ldh, const float* slab, int ksplit, int lo8, llmi_stream_t stream) {
     return rows_split_launch(x, ldx, m, k, gamma, g_dtype, eps, static_cast<_Float16*>(hi), static_cast<_Float16*>(lo),

@@ -301,6 +301,11 @@ struct Engine {
     // default 1) where w8_prefill_supported(); 0 keeps them on gemm.hip
     bool w8_gemm = true;
     bool w8_prefill_supported() const;
+    // int4 weights: the same layers with q/k/v, gate_up and down on gemm_w4.hip (the nibbles and
+    // group scales the decode GEMVs read, no second copy) and the int8 W_o on gemm_w8.hip, where
+    // w4_prefill_supported(). Option "w4_gemm", default 0: an int4 engine refuses prefill
+    bool w4_gemm = false;
+    bool w4_prefill_supported() const;
     // split mode 3: e4m3 copies of the prefill GEMM weights (W * 2^exp, gemm3.hip), made on first use
     struct W8Layer {
         void *qkv = nullptr, *o = nullptr, *gu = nullptr, *down = nullptr;

@@ -408,8 +408,12 @@ int Engine::set_option(const std::string& name, int value) {
     } else if (name == "w8_gemm") {
         LLMI_REQUIRE(value == 0 || value == 1, "set_option w8_gemm: 1 int8 prefill on gemm_w8 (default), 0 on gemm");
         w8_gemm = value == 1;
+    } else if (name == "w4_gemm") {
+        LLMI_REQUIRE(value == 0 || value == 1, "set_option w4_gemm: 1 int4 prefill on gemm_w4, 0 none (default)");
+        w4_gemm = value == 1;
     } else {
-        LLMI_REQUIRE(false, "set_option: unknown option (kpar, qkv_attn, qa_o, qa_grid, qa_order, qa_poll, w8_gemm)");
+        LLMI_REQUIRE(false,
+                     "set_option: unknown option (kpar, qkv_attn, qa_o, qa_grid, qa_order, qa_poll, w8_gemm, w4_gemm)");
     }
     return invalidate();
 }

@@ -89,6 +89,24 @@ bool Engine::w8_prefill_supported() const {
            gemm_w8_supported(c.hidden, il, EPI_SLAB, w8_slices(il)) && c.head_dim % 64 == 0;
 }
 
+// int4 weights: g's launch on gemm_w4.hip with the weight's group scales [n][k / 128]
+static int w4_launch(const Gemm2Args& g, const __half* scales, hipStream_t s) {
+    GemmW4Args a;
+    a.a[0] = g.a[0]; a.a[1] = g.a[1]; a.planes = g.planes; a.lda = g.lda;
+    a.w = g.w; a.scales = scales; a.m = g.m; a.n = g.n; a.k = g.k;
+    a.epi = g.epi; a.pair_off = g.pair_off;
+    a.y = g.y; a.y_hi = g.y_hi; a.y_lo = g.y_lo; a.ldy = g.ldy;
+    a.ksplit = g.ksplit; a.slab = g.slab;
+    return gemm_w4_launch(a, s);
+}
+// (the int8 W_o of an int4 engine keeps gemm_w8's shape rule and slices)
+bool Engine::w4_prefill_supported() const {
+    return wdt == LLMI_I4 && gemm_w4_supported(ql + 2 * kvrows, c.hidden, EPI_STORE, 1) &&
+           gemm_w8_supported(c.hidden, ql, EPI_SLAB, w8_slices(ql)) &&
+           gemm_w4_supported(2 * il, c.hidden, EPI_SILU_MUL, 1) &&
+           gemm_w4_supported(c.hidden, il, EPI_SLAB, w8_slices(il)) && c.head_dim % 64 == 0;
+}
+
 // rope + KV write + causal attention of rows [p0, p0 + m) of layer l: the fields both prefill
 // paths share
 PrefillAttnArgs Engine::prefill_attn_args(int l, int m, int p0) const {
@@ -105,11 +123,17 @@ PrefillAttnArgs Engine::prefill_attn_args(int l, int m, int p0) const {
 // One prefill layer on the LDS-DMA GEMM (gemm2.hip): RMSNorm + split into fp16
 // planes, q/k/v GEMM, rope + KV write + causal attention, split, o_proj (+residual),
 // RMSNorm + split, gate_up GEMM writing silu(g) * u as planes, down (+residual). int8 weights:
-// the same launches with every GEMM on gemm_w8.hip (128 x 128 tiles; no gemm3 form).
+// the same launches with every GEMM on gemm_w8.hip (128 x 128 tiles; no gemm3 form). int4 weights:
+// q/k/v, gate_up and down on gemm_w4.hip, the int8 W_o on gemm_w8.hip.
 int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     const Layer& L = layers[l];
     const int H = c.hidden;
-    const bool i8 = wdt == LLMI_I8;
+    const bool i4 = wdt == LLMI_I4;
+    const bool qw = wdt == LLMI_I8 || i4;  // quantised: no gemm3 form, whole-group K slices
+    // a quantised engine's launch of g: by the weight's own format
+    auto qlaunch = [&](const Gemm2Args& g, const __half* scales, bool is_o) {
+        return i4 && !is_o ? w4_launch(g, scales, stream) : w8_launch(g, scales, stream);
+    };
     // split 3: the lo planes are e4m3 bytes against the e4m3 weight copies (gemm3.hip)
     const bool f8 = split == 3;
     const W8Layer* W8 = f8 ? &w8l[l] : nullptr;
@@ -123,13 +147,13 @@ int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     g.lda = H; g.w = L.qkv; g.n = ql + 2 * kvrows; g.k = H;
     g.ldy = g.n;
     if (f8) { g.w8 = W8->qkv; g.w8_exp = W8->qkv_e; }
-    const bool qkv3 = !i8 && gemm3_supported(g.n, H, EPI_SLAB, 2);
+    const bool qkv3 = !qw && gemm3_supported(g.n, H, EPI_SLAB, 2);
     if (qkv3) {  // two K slices (96 tiles alone would leave most CUs idle)
         g.epi = EPI_SLAB; g.ksplit = 2; g.slab = pf_qkv;
         LLMI_TRY(gemm3_launch(g, stream));
     } else {
         g.epi = EPI_STORE; g.y = pf_qkv;
-        LLMI_TRY(i8 ? w8_launch(g, L.qkv_s, stream) : gemm2_launch(g, stream));
+        LLMI_TRY(qw ? qlaunch(g, L.qkv_s, false) : gemm2_launch(g, stream));
     }
     // rope (+ the second qkv slice) + kv write + causal attention
     PrefillAttnArgs pa = prefill_attn_args(l, m, p0);
@@ -148,14 +172,14 @@ int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     // split-K into slabs (128 tiles alone would leave half the CUs idle); the next
     // rows_split adds the slices into x in slice order (deterministic). The fp8 lo
     // pass is gemm3's: 8 slices of 256 x 256 tiles (256 workgroups)
-    int so = i8 ? w8_slices(ql) : (ql % (kPfSplit * 64)) == 0 ? kPfSplit : 1;
+    int so = qw ? w8_slices(ql) : (ql % (kPfSplit * 64)) == 0 ? kPfSplit : 1;
     g.lda = ql; g.w = L.o; g.w_kblock = 0; g.n = H; g.k = ql;
     g.epi = EPI_SLAB; g.ksplit = so; g.slab = pf_slab; g.y = pf_x; g.ldy = H;
     if (f8) {
         so = kPfDown; g.ksplit = so; g.w8 = W8->o; g.w8_exp = W8->o_e;
         LLMI_TRY(gemm3_launch(g, stream));
     } else {  // (the fp16 o_proj on gemm3's 8 K slices measured 0.1 ms slower a 7B prefill, r07l)
-        LLMI_TRY(i8 ? w8_launch(g, L.o_s, stream) : gemm2_launch(g, stream));
+        LLMI_TRY(qw ? qlaunch(g, L.o_s, true) : gemm2_launch(g, stream));
     }
     g.w_kblock = 0;
     // (o slices into x) + rmsnorm + gate_up + silu * up -> planes of the down GEMM's input
@@ -170,12 +194,12 @@ int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     g.sk_slab = nullptr; g.sk_flags = nullptr; g.sk_grid = 0;
     // the whole K work of gate_up's 172 tiles spread evenly over every CU (gemm3 stream-K),
     // the fp8 lo pass included
-    const bool gu3 = !i8 && gemm3_supported(g.n, H, EPI_SILU_MUL, 1);
+    const bool gu3 = !qw && gemm3_supported(g.n, H, EPI_SILU_MUL, 1);
     if (gu3) {
         g.err = &st->error;
         (void)gemm3_sk_attach(g, stream);
     }
-    LLMI_TRY(gu3 ? gemm3_launch(g, stream) : i8 ? w8_launch(g, L.gu_s, stream) : gemm2_launch(g, stream));
+    LLMI_TRY(gu3 ? gemm3_launch(g, stream) : qw ? qlaunch(g, L.gu_s, false) : gemm2_launch(g, stream));
     // down + residual: K slices into slabs (gemm3: 8 uneven slices, 256 workgroups)
     g.sk_slab = nullptr; g.sk_flags = nullptr; g.sk_grid = 0;
     g.a[0] = pf_act_h(); g.a[1] = split >= 2 ? pf_act_l() : nullptr;
@@ -183,9 +207,9 @@ int Engine::prefill_layer_gemm2(int l, int m, int p0, int split) {
     if (f8) { g.w8 = W8->down; g.w8_exp = W8->down_e; }
     g.epi = EPI_SLAB; g.pair_off = 0; g.y = pf_x; g.y_hi = g.y_lo = nullptr; g.ldy = H; g.slab = pf_slab;
     int sd;
-    if (i8) {
+    if (qw) {
         sd = w8_slices(il); g.ksplit = sd;
-        LLMI_TRY(w8_launch(g, L.down_s, stream));
+        LLMI_TRY(qlaunch(g, L.down_s, false));
     } else if (gemm3_supported(H, il, EPI_SLAB, kPfDown)) {
         sd = kPfDown; g.ksplit = sd;
         LLMI_TRY(gemm3_launch(g, stream));
@@ -271,8 +295,15 @@ int Engine::scored_logits_out(int pos, float* out, int n) {
 }
 
 int Engine::prefill(int n, int split, bool scored) {
-    if (wdt == LLMI_I4) {
+    const bool i4 = wdt == LLMI_I4;
+    if (i4 && !(pf_from ? pf_from : this)->w4_gemm) {
         set_last_error("[llmi][ERROR] prefill: int4 engines have no prefill GEMMs (run the prompt as decode steps)");
+        return LLMI_EUNSUPPORTED;
+    }
+    if (i4 && !w4_prefill_supported()) {
+        set_last_error("[llmi][ERROR] prefill: the int4 prefill GEMMs (option w4_gemm) need q/k/v, hidden and gate_up "
+                       "rows in multiples of 128, every projection's K per K slice a multiple of 128 and at most "
+                       "24576, and head_dim a multiple of 64; run the prompt as decode steps");
         return LLMI_EUNSUPPORTED;
     }
     LLMI_REQUIRE(!grouped && c.tp_world == 1, "prefill: tensor-parallel prefill is not supported");
@@ -281,15 +312,16 @@ int Engine::prefill(int n, int split, bool scored) {
     LLMI_REQUIRE(split >= 1 && split <= 3,
                  "prefill: split must be 1 (fp16 A), 2 (fp32-faithful) or 3 (fp16 hi + fp8 lo planes)");
     LLMI_REQUIRE(!scored || (lp_top >= 0 && lp_buf), "prefill_scored: set_logprobs first");
-    if (!gemm_supported(wdt, ql + 2 * kvrows, c.hidden, EPI_STORE) || !gemm_supported(wdt, c.hidden, ql, EPI_ADD) ||
-        !gemm_supported(wdt, 2 * il, c.hidden, EPI_SILU_MUL) || !gemm_supported(wdt, c.hidden, il, EPI_ADD))
+    // (gemm.hip knows nothing of int4: an int4 engine past the gate above runs gemm_w4 / gemm_w8 alone)
+    if (!i4 && (!gemm_supported(wdt, ql + 2 * kvrows, c.hidden, EPI_STORE) || !gemm_supported(wdt, c.hidden, ql, EPI_ADD) ||
+                !gemm_supported(wdt, 2 * il, c.hidden, EPI_SILU_MUL) || !gemm_supported(wdt, c.hidden, il, EPI_ADD)))
         return decode(n, 1);  // fp32 weights / odd shapes: the decode kernels, one row at a time
     const bool use_gemm2 = wdt == LLMI_F16 && gemm2_supported(ql + 2 * kvrows, c.hidden, EPI_STORE) &&
                            gemm2_supported(c.hidden, ql, EPI_ADD) && gemm2_supported(2 * il, c.hidden, EPI_SILU_MUL) &&
                            gemm2_supported(c.hidden, il, EPI_ADD) && c.head_dim % 64 == 0;
     // int8 weights: the same layer function on gemm_w8.hip's GEMMs (option "w8_gemm" 0: gemm.hip, below)
     const bool use_w8 = (pf_from ? pf_from : this)->w8_gemm && w8_prefill_supported();
-    const bool layers_gemm2 = use_gemm2 || use_w8;
+    const bool layers_gemm2 = use_gemm2 || use_w8 || i4;
     // no GEMM form for the lm_head shape: decode steps, which score every row themselves
     // (an int8 engine's fp16 lm_head stays on gemm.hip with either layer route)
     if (scored && !head_gemm_supported(use_gemm2)) return decode(n, 1);

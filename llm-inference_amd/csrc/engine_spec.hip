@@ -362,7 +362,7 @@ int Engine::draft_catch_up(const int32_t* hist, int p, int use_prefill, int use_
     }
     const int rows = p - m;
     if (rows == 0) return LLMI_OK;
-    if (use_prefill && rows > 1 && wdt != LLMI_I4) return prefill(rows, 2);
+    if (use_prefill && rows > 1 && (wdt != LLMI_I4 || w4_gemm)) return prefill(rows, 2);
     return decode(rows, use_graph);
 }
 

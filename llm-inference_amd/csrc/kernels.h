@@ -237,6 +237,31 @@ struct GemmW8Args {
 bool gemm_w8_supported(int n, int k, int epi, int ksplit);
 // LLMI_EUNSUPPORTED, nothing launched, for a shape or epilogue gemm_w8_supported refuses
 int gemm_w8_launch(GemmW8Args a, hipStream_t s);
+// The same GEMM for 4-bit group-quantised weights in the decode GEMVs' format (gemm_w4.hip):
+// Y (op)= sum_g fp32(s[n, g]) * sum_{k in g} sum_p A_p[m, k] q[n, k], each group's fp32 sum scaled
+// in fp32; no epilogue scale.
+struct GemmW4Args {
+    const _Float16* a[2] = {nullptr, nullptr};  // [m, lda] planes (lda >= k)
+    int planes = 2;
+    int lda = 0;
+    const void* w = nullptr;          // [n, k / 2] nibbles q + 8, the even column low
+    const __half* scales = nullptr;   // [n][k / 128]
+    int m = 0, n = 0, k = 0;
+    int epi = EPI_STORE;              // EPI_STORE, EPI_SLAB, EPI_SILU_MUL
+    int pair_off = 0;
+    float* y = nullptr;               // [m, ldy] fp32
+    _Float16* y_hi = nullptr;         // EPI_SILU_MUL: write the result as fp16 planes instead
+    _Float16* y_lo = nullptr;
+    int ldy = 0;
+    int ksplit = 1;                   // EPI_SLAB: K slices of whole groups
+    float* slab = nullptr;            // EPI_SLAB: [ksplit][m][ldy], slice i its own groups' scaled sum
+    int n_tiles = 0;                  // set by gemm_w4_launch
+};
+// N as gemm_w8_supported; K / ksplit (ksplit counts under EPI_SLAB only) a multiple of 128 and at
+// most 24576 (the tile's scales are staged in LDS beside the rings)
+bool gemm_w4_supported(int n, int k, int epi, int ksplit);
+// LLMI_EUNSUPPORTED, nothing launched, for a shape or epilogue gemm_w4_supported refuses
+int gemm_w4_launch(GemmW4Args a, hipStream_t s);
 constexpr int kSkCtlWords = 64;    // stream-K control words ahead of the flags (256 B)
 // the next `launches` stream-K launches run with sk_test = mode (llmi_debug_stream_k)
 void gemm3_sk_debug(int mode, int launches);

@@ -107,6 +107,14 @@ class DebugGemmW8Args(C.Structure):
                 ("y_lo", C.c_void_p), ("ldy", C.c_int), ("ksplit", C.c_int), ("slab", C.c_void_p)]
 
 
+class DebugGemmW4Args(C.Structure):
+    """llmi_debug_gemm_w4_args (include/llmi.h), field for field."""
+    _fields_ = [("a_hi", C.c_void_p), ("a_lo", C.c_void_p), ("planes", C.c_int), ("lda", C.c_int),
+                ("w", C.c_void_p), ("scales", C.c_void_p), ("m", C.c_int), ("n", C.c_int), ("k", C.c_int),
+                ("epi", C.c_int), ("pair_off", C.c_int), ("y", C.c_void_p), ("y_hi", C.c_void_p),
+                ("y_lo", C.c_void_p), ("ldy", C.c_int), ("ksplit", C.c_int), ("slab", C.c_void_p)]
+
+
 _P, _I, _U64, _U32, _F, _SZ =C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_float, C.c_size_t
 _SIGS = {
     "llmi_last_error": (C.c_char_p, []),
@@ -161,6 +169,7 @@ _SIGS = {
     "llmi_debug_gemm1": (_I, [C.POINTER(DebugGemm1Args), _P]),
     "llmi_debug_gemm1_plan": (_I, [C.POINTER(DebugGemm1Args), C.POINTER(_I), C.POINTER(_I)]),
     "llmi_debug_gemm_w8": (_I, [C.POINTER(DebugGemmW8Args), _P]),
+    "llmi_debug_gemm_w4": (_I, [C.POINTER(DebugGemmW4Args), _P]),
     "llmi_debug_rows_split": (_I, [_P, _I, _I, _I, _P, _I, _F, _P, _P, _I, _P, _I, _I, _P]),
     "llmi_debug_w8_prepare": (_I, [_P, _I, _I, _P, C.POINTER(_I), _P]),
     "llmi_hbm_read_bench": (_I, [_SZ, _I, _P, _P, _P]),

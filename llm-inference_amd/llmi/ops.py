@@ -685,6 +685,14 @@ def debug_gemm_w8(**fields) -> None:
     call("llmi_debug_gemm_w8", ctypes.byref(a), _stream())
 
 
+def debug_gemm_w4(**fields) -> None:
+    """llmi_debug_gemm_w4 (test hook): one launch of the int4-weight prefill GEMM (gemm_w4.hip)
+    with llmi_debug_gemm_w4_args filled from the keywords (tensors become their device addresses;
+    the rest stays zero)."""
+    a = _debug_args(_lib.DebugGemmW4Args, fields)
+    call("llmi_debug_gemm_w4", ctypes.byref(a), _stream())
+
+
 def debug_rows_split(x, m: int, k: int, hi=None, lo=None, ldx: int = 0, ldh: int = 0, gamma=None,
                      eps: float = 1e-5, slab=None, ksplit: int = 0, lo8: bool = False) -> None:
     """llmi_debug_rows_split (test hook): rows_split_launch on device tensors (ldx / ldh 0: k)."""
