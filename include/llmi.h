@@ -222,6 +222,20 @@ int llmi_debug_gemv_plan(const llmi_debug_gemv_args* args, int* grid, int* unrol
  * without RMSNorm (any epilogue) or x_fixed with RMSNorm (epi 0, 2, 3); other input forms and
  * kpar > 1 return LLMI_EUNSUPPORTED; m outside 2..8 LLMI_EINVAL. Nothing is launched on an error. */
 int llmi_debug_gemv_rows(const llmi_debug_gemv_args* args, int m, llmi_stream_t stream);
+/* llmi_debug_gemv_rows_mfma: the same launch on the matrix cores (csrc/gemv_rows_mfma.hip), the
+ * kernel behind llmi_batch_set_option "rows_mfma" -- args[0 .. m), 1 <= m <= 8, checked as
+ * llmi_debug_gemv_rows checks them, in ONE launch at every k. x enters the MFMA as two fp16
+ * planes (hi = fp16(x * gamma), lo = fp16(x * gamma - hi)), so a row is faithful to fp32 (rel-L2
+ * well under 2e-6 against float64) but NOT bitwise llmi_debug_gemv's; x_out and seed_dst are
+ * bitwise. Row i's outputs are the same bits whatever m is, wherever the row sits in args and
+ * whatever the other rows hold. Served: w_dtype f16 / i8 with x_fixed + RMSNorm and epi 0 / 2,
+ * or an fp32 x without RMSNorm and epi 4 (yacc_single, or ksplit slices); k (of a slice) a
+ * multiple of 32 and <= 13824 (i8 and epi 2: 11264); any n_rows and pair_off. Precondition, not
+ * checked: |x * gamma| (epi 4: |x|) < 65504, the range of the hi plane; beyond it hi is inf and
+ * lo NaN. Everything else -- epi 1
+ * and 3, f32 / int4 weights, kpar > 1, ldw -- returns LLMI_EUNSUPPORTED with a message; nothing
+ * is launched on an error. */
+int llmi_debug_gemv_rows_mfma(const llmi_debug_gemv_args* args, int m, llmi_stream_t stream);
 
 /* llmi_debug_attn_oproj: one layer's decode attention as the engine's separate launches run
  * it -- the split-KV attention leaving its partials in `workspace` (no merge kernel), then the
@@ -1262,6 +1276,18 @@ int llmi_batch_load_bin(llmi_batch* b, const char* weight_path);
 int llmi_batch_load_bin_quantized(llmi_batch* b, const char* weight_path);
 int llmi_batch_set_prompt(llmi_batch* b, int seq, const int32_t* ids, int n);
 int llmi_batch_reset(llmi_batch* b, int seq);
+/* Batch options (same-process A/B, as llmi_engine_set_option is for an engine). One name:
+ *   "rows_mfma" 0 (default) / 1: the q/k/v, gate_up and down projections of a step run on the
+ * matrix cores (csrc/gemv_rows_mfma.hip: one launch at every k, x as two fp16 planes) wherever
+ * that kernel serves the shape -- fp16 / int8 weights, k a multiple of 32 -- and as before
+ * elsewhere; for every number of active slots, one included. With 1 a slot's logits are
+ * faithful to fp32 but no longer bitwise the engine's; they still do not depend on the other
+ * slots (which are active, what they hold), and a run repeats bit for bit. The lm_head,
+ * attention, o_proj, samplers, prefill and fork are unchanged. Precondition with 1, not checked:
+ * the normalised activations |x * gamma| and the FFN's |act| stay below 65504 (fp16 hi plane).
+ * The call drops the batch's captured steps. LLMI_EINVAL with a message for an unknown name or
+ * another value; the batch stays usable. */
+int llmi_batch_set_option(llmi_batch* b, const char* name, int value);
 /* llmi_engine_edit of slot seq's sequence, on the batch's stream: the slot goes on bitwise as
  * the edited engine would alone, the other slots as if nothing happened. LLMI_EINVAL for a seq
  * out of range, an idle slot, and llmi_engine_edit's own. */

@@ -145,26 +145,42 @@ int llmi_debug_gemv_plan(const llmi_debug_gemv_args* args, int* grid, int* unrol
     return gemv_plan(debug_gemv_args(*args), grid, unroll, xpt);
 }
 
-int llmi_debug_gemv_rows(const llmi_debug_gemv_args* args, int m, llmi_stream_t stream) {
-    LLMI_REQUIRE(args != nullptr, "debug_gemv_rows: null arguments");
-    LLMI_REQUIRE(m >= 2 && m <= kGemvRowsMax, "debug_gemv_rows: m must be 2..8");
-    GemvRowsArgs p;
+namespace {
+// args[0 .. m) as one multi-row launch's arguments (llmi_debug_gemv_rows / _rows_mfma)
+int debug_rows_args(const llmi_debug_gemv_args* args, int m, GemvRowsArgs& p) {
     for (int i = 0; i < m; ++i) {
         const llmi_debug_gemv_args& d = args[i];
         const llmi_debug_gemv_args& z = args[0];
-        LLMI_REQUIRE(d.epi >= EPI_STORE && d.epi <= EPI_ATOMIC, "debug_gemv_rows: epi must be 0..4");
+        LLMI_REQUIRE(d.epi >= EPI_STORE && d.epi <= EPI_ATOMIC, "debug_gemv_rows / debug_gemv_rows_mfma: epi must be 0..4");
         LLMI_REQUIRE(d.grid >= 0 && d.seed_n >= 0 && (!d.seed_dst || !d.seed_keep || d.seed_src),
-                     "debug_gemv_rows: bad grid or seed arguments");
+                     "debug_gemv_rows / debug_gemv_rows_mfma: bad grid or seed arguments");
         LLMI_REQUIRE(d.w == z.w && d.scales == z.scales && d.w_dtype == z.w_dtype && d.n_rows == z.n_rows &&
                          d.k == z.k && d.ldw == z.ldw && d.gamma == z.gamma && d.g_dtype == z.g_dtype &&
                          d.eps == z.eps && d.epi == z.epi && d.resid_scale == z.resid_scale &&
                          d.pair_off == z.pair_off && d.idx_base == z.idx_base && d.grid == z.grid &&
                          d.ksplit == z.ksplit && d.yacc_single == z.yacc_single && d.seed_n == z.seed_n &&
                          d.seed_keep == z.seed_keep && d.kpar == z.kpar,
-                     "debug_gemv_rows: the rows must share every weight-side, shape and epilogue field");
+                     "debug_gemv_rows / debug_gemv_rows_mfma: the rows must share every weight-side, shape and epilogue field");
         gemv_rows_add(p, debug_gemv_args(d));
     }
+    return LLMI_OK;
+}
+}  // namespace
+
+int llmi_debug_gemv_rows(const llmi_debug_gemv_args* args, int m, llmi_stream_t stream) {
+    LLMI_REQUIRE(args != nullptr, "debug_gemv_rows: null arguments");
+    LLMI_REQUIRE(m >= 2 && m <= kGemvRowsMax, "debug_gemv_rows: m must be 2..8");
+    GemvRowsArgs p;
+    LLMI_TRY(debug_rows_args(args, m, p));
     return gemv_rows_launch(p, STREAM(stream));
+}
+
+int llmi_debug_gemv_rows_mfma(const llmi_debug_gemv_args* args, int m, llmi_stream_t stream) {
+    LLMI_REQUIRE(args != nullptr, "debug_gemv_rows_mfma: null arguments");
+    LLMI_REQUIRE(m >= 1 && m <= kGemvRowsMax, "debug_gemv_rows_mfma: m must be 1..8");
+    GemvRowsArgs p;
+    LLMI_TRY(debug_rows_args(args, m, p));
+    return gemv_rows_mfma_launch(p, STREAM(stream));
 }
 
 int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t stream) {

@@ -561,7 +561,9 @@ struct Group {
 // active slots runs every slot's step_start, then per layer ONE multi-row GEMV (gemv_rows.hip)
 // for q/k/v, the existing attention + o_proj launches per slot (that slot's own position and
 // split count), ONE multi-row GEMV for gate_up and ONE for down, then ONE for the lm_head and
-// each slot's sampler. The multi-row GEMV gives every row bitwise the single-row result, and
+// each slot's sampler. (With the option "rows_mfma" q/k/v, gate_up and down go through
+// gemv_rows_mfma.hip instead, for one active slot too: faithful, slot-independent, not bitwise.)
+// The multi-row GEMV gives every row bitwise the single-row result, and
 // everything else is the engine's own launch, so a slot's tokens and logits are bitwise those
 // of an Engine decoding the sequence alone. W_o is still streamed once per slot. A slot's prompt
 // can run through the engine's own (scored) prefill, one slot per call, on slot 0's prefill
@@ -573,12 +575,15 @@ struct Batch {
     // a setter call (a slot's setter drops the cache: Engine::invalidate)
     static constexpr size_t kMaxGraphs = 64;
     BatchGraphs graphs{kMaxGraphs};
+    // set_option "rows_mfma": q/k/v, gate_up and down on gemv_rows_mfma_launch where it serves them
+    bool rows_mfma = false;
 
     ~Batch();
     int init(const llmi_config& cfg, int n_seq, int dev);
     int slot_ok(int seq) const;
     int loaded();
     int reset(int seq);
+    int set_option(const std::string& name, int value);
     std::vector<int> active() const;
     int record_step(const std::vector<int>& act);
     int decode(int n, int use_graph);

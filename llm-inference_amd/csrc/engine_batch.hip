@@ -38,6 +38,13 @@ int Batch::reset(int seq) {
     r[seq]->host_next_pos = 0;
     return LLMI_OK;
 }
+int Batch::set_option(const std::string& name, int value) {
+    LLMI_REQUIRE(name == "rows_mfma", "batch set_option: unknown option (rows_mfma)");
+    LLMI_REQUIRE(value == 0 || value == 1,
+                 "batch set_option rows_mfma: 1 q/k/v, gate_up and down on the matrix cores, 0 off (default)");
+    rows_mfma = value != 0;
+    return graphs.drop(stream);  // the captured steps hold the other kernels
+}
 std::vector<int> Batch::active() const {
     std::vector<int> a;
     for (int i = 0; i < (int)r.size(); ++i)
@@ -53,7 +60,7 @@ int Batch::record_step(const std::vector<int>& act) {
     auto rows = [&](auto&& args_of) { return gemv_rows_of(es, stream, args_of); };
     for (Engine* e : es) LLMI_TRY(e->rec_start());
     const int L = r[0]->c.layers;
-    if (es.size() == 1) {  // one sequence: the engine's own single-row launches
+    if (es.size() == 1 && !rows_mfma) {  // one sequence: the engine's own single-row launches
         Engine& e = *es[0];
         for (int l = 0; l < L; ++l) {
             LLMI_TRY(e.rec_attn(l));
@@ -61,15 +68,28 @@ int Batch::record_step(const std::vector<int>& act) {
         }
         return e.rec_head();
     }
+    // option rows_mfma: the three projections on the matrix cores where the kernel serves them
+    // (debug stamps cleared as gemv_rows_of does), else the multi-row GEMV -- one slot: the
+    // single-row GEMV with the engine's own arguments, stamps and all; the `tiny` preset of the
+    // tests is served everywhere, so no test reaches either fallback
+    auto proj = [&](auto&& args_of) {
+        if (!rows_mfma) return rows(args_of);
+        GemvRowsArgs p;
+        for (Engine* e : es) gemv_rows_add(p, args_of(*e));
+        p.a.stamps = nullptr;
+        if (gemv_rows_mfma_supported(p)) return gemv_rows_mfma_launch(p, stream);
+        return p.m == 1 ? gemv_launch(args_of(*es[0]), stream) : rows(args_of);
+    };
     for (int l = 0; l < L; ++l) {
-        LLMI_TRY(rows([&](Engine& e) { return e.qkv_args(l); }));
+        LLMI_TRY(proj([&](Engine& e) { return e.qkv_args(l); }));
         for (Engine* e : es) {
             const AttnArgs at = e->attn_args(l);
             LLMI_TRY(e->rec_oproj(LLMI_OK, e->o_args(l), &at));
         }
-        LLMI_TRY(rows([&](Engine& e) { return e.gu_args(l); }));
-        LLMI_TRY(rows([&](Engine& e) { return e.down_args(l); }));
+        LLMI_TRY(proj([&](Engine& e) { return e.gu_args(l); }));
+        LLMI_TRY(proj([&](Engine& e) { return e.down_args(l); }));
     }
+    if (es.size() == 1) return es[0]->rec_head();  // (option on: one slot takes the same projections)
     LLMI_TRY(rows([&](Engine& e) { return e.lm_args(); }));
     for (Engine* e : es) LLMI_TRY(e->rec_sample());
     return LLMI_OK;

@@ -596,6 +596,12 @@ int llmi_batch_reset(llmi_batch* b, int seq) {
     return b->b.reset(seq);
 }
 
+int llmi_batch_set_option(llmi_batch* b, const char* name, int value) {
+    LLMI_REQUIRE(b && name, "batch set_option: null argument");
+    LLMI_HIP(hipSetDevice(b->b.r[0]->device));
+    return b->b.set_option(name, value);
+}
+
 int llmi_batch_set_sampling_params(llmi_batch* b, int seq, const llmi_sampling_params* p) {
     LLMI_REQUIRE(b && p, "batch_set_sampling_params: null batch or params");
     LLMI_TRY(b->b.slot_ok(seq));

@@ -141,6 +141,17 @@ int gemv_rows_launch(const GemvRowsArgs& p, hipStream_t s);
 // are run as several launches
 int gemv_rows_fit(const GemvArgs& a);
 
+// The same on the matrix cores (gemv_rows_mfma.hip), m = 1..kGemvRowsMax in ONE launch at every
+// k: x enters as two fp16 planes (hi + lo), so row i is fp32-faithful but NOT bitwise
+// gemv_launch's. Row i's result is the same bits whatever m is, wherever the row sits in
+// p.row and whatever the other rows hold. Served: fp16 / int8 weights with a fixed-point x +
+// RMSNorm and the store / silu epilogues (x_out and the seed hand-over included), or an fp32 x
+// with the atomic epilogue (yacc_single or ksplit); k (of a K slice) a multiple of 32, <= 13824.
+bool gemv_rows_mfma_supported(const GemvRowsArgs& p);
+// LLMI_EUNSUPPORTED with a message, nothing launched, for what gemv_rows_mfma_supported refuses:
+// the argmax epilogue, fp32 / int4 weights, kpar, granule rows, exchange tails, stamps, ldw
+int gemv_rows_mfma_launch(const GemvRowsArgs& p, hipStream_t s);
+
 // ------------------------------------------------------ prefill GEMM (MFMA)
 // Y[m, n] (op)= sum_k A[m, k] W[n, k] for M prompt rows; see gemm.hip.
 struct GemmArgs {

@@ -157,6 +157,7 @@ _SIGS = {
     "llmi_debug_stream_k": (_I, [_I, _I]),
     "llmi_debug_gemv": (_I, [C.POINTER(DebugGemvArgs), _P]),
     "llmi_debug_gemv_rows": (_I, [C.POINTER(DebugGemvArgs), _I, _P]),
+    "llmi_debug_gemv_rows_mfma": (_I, [C.POINTER(DebugGemvArgs), _I, _P]),
     "llmi_debug_gemv_plan": (_I, [C.POINTER(DebugGemvArgs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "llmi_debug_attn_oproj": (_I, [C.POINTER(DebugAttnOprojArgs), _P]),
     "llmi_debug_attn_oproj_rows": (_I, [C.POINTER(DebugAttnOprojArgs), _I, _P]),
@@ -260,6 +261,7 @@ _SIGS = {
     "llmi_batch_load_bin_quantized": (_I, [_P, C.c_char_p]),
     "llmi_batch_set_prompt": (_I, [_P, _I, _P, _I]),
     "llmi_batch_reset": (_I, [_P, _I]),
+    "llmi_batch_set_option": (_I, [_P, C.c_char_p, _I]),
     "llmi_batch_fork": (_I, [_P, _I, _P, _I, _I, _P, _I]),
     "llmi_batch_set_sampling_params": (_I, [_P, _I, _P]),
     "llmi_batch_set_logprobs": (_I, [_P, _I, _I]),

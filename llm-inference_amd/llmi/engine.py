@@ -581,6 +581,11 @@ class Batch:
         call("llmi_batch_reset", self._h, int(seq))
         self._plen[int(seq)], self._pos[int(seq)] = 0, 0
 
+    def set_option(self, name: str, value: int):
+        """llmi_batch_set_option: "rows_mfma" 1 runs the q/k/v, gate_up and down projections on the
+        matrix cores (fp32-faithful and slot-independent, not bitwise the engine's); 0 (default) off."""
+        call("llmi_batch_set_option", self._h, name.encode(), int(value))
+
     def edit(self, seq: int, keep: int, ids):
         """Engine.edit for one slot (llmi_batch_edit); the other slots are left where they are."""
         ids = np.ascontiguousarray(ids, dtype=np.int32)

@@ -593,6 +593,18 @@ def debug_gemv_rows(rows) -> None:
     call("llmi_debug_gemv_rows", arr, len(rows), _stream())
 
 
+def debug_gemv_rows_mfma(rows) -> None:
+    """llmi_debug_gemv_rows_mfma (test hook): the same rows (1..8) as ONE launch of the matrix-core
+    multi-row GEMV (gemv_rows_mfma.hip): fp32-faithful, not bitwise debug_gemv's; row i's outputs
+    do not depend on the other rows or on its place among them."""
+    arr = (_lib.DebugGemvArgs * max(len(rows), 1))()
+    for i, fields in enumerate(rows):
+        fields = dict(fields)
+        fields.setdefault("resid_scale", 1.0)
+        arr[i] = _debug_args(_lib.DebugGemvArgs, fields)
+    call("llmi_debug_gemv_rows_mfma", arr, len(rows), _stream())
+
+
 def debug_gemv_plan(**fields):
     """llmi_debug_gemv_plan (test hook): (grid, unroll, xpt) llmi_debug_gemv would use for the
     same keywords; launches nothing."""
