@@ -247,7 +247,13 @@ int llmi_debug_gemv_rows_mfma(const llmi_debug_gemv_args* args, int m, llmi_stre
  * one layer [kv_heads, max_seq, head_dim] of cache_dtype; slot *pos_dev is written. w: W_o
  * [n_rows, ldw] (ldw >= heads * head_dim: a column shard of a wider matrix), or head_major
  * [heads][n_rows][head_dim]; per-row fp16 `scales` for int8. head_dim 0 -> 128, rope_base
- * 0 -> 10000. The caller owns every buffer, `workspace` (llmi_attn_workspace_bytes) included. */
+ * 0 -> 10000. The caller owns every buffer, `workspace` (llmi_attn_workspace_bytes) included.
+ * gqa 0: the scalar kernel (one workgroup per query head and split). gqa 1: the kernel behind
+ * the option "gqa_attn" -- one workgroup per (kv head, split) on the matrix cores, the same
+ * partials, cache row, xacc seed and error bits, faithful to fp32 (4e-6 rel-L2) but not bitwise
+ * gqa 0's; it serves head_dim 128, 2 <= heads / kv_heads <= 8 and an f16 or i8 cache, and
+ * anything else returns LLMI_EUNSUPPORTED with a message and launches nothing.
+ * (llmi_debug_attn_oproj_rows ignores the field.) */
 typedef struct llmi_debug_attn_oproj_args {
     const float* qkv;
     void* k_cache;
@@ -269,6 +275,7 @@ typedef struct llmi_debug_attn_oproj_args {
     int* err;
     void* k_scale; /* cache_dtype LLMI_I8 (KV8): the layer's fp16 row scales [kv_heads, max_seq]; */
     void* v_scale; /* NULL: unused (an f16 / f32 cache) */
+    int gqa;       /* 1: the attention launch is the grouped-query kernel (csrc/attn_gqa.hip), see above */
 } llmi_debug_attn_oproj_args;
 int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t stream);
 /* llmi_debug_attn_oproj_rows: the multi-row attention + o_proj of a speculative verify step --
@@ -1209,7 +1216,15 @@ int llmi_engine_xchg_loopback(llmi_engine* e);
  * decode GEMVs' nibbles and group scales in place) and the int8 W_o on gemm_w8.hip, for the
  * prefill, the scored prefill and a draft engine's catch-up; a shape those GEMMs refuse (rows not
  * in multiples of 128, head_dim not a multiple of 64) is LLMI_EUNSUPPORTED. 0 (default): an int4
- * engine refuses prefill and runs its prompt as decode steps. */
+ * engine refuses prefill and runs its prompt as decode steps.
+ * "gqa_attn": 1 runs the decode attention of a grouped-query model on the matrix cores
+ * (csrc/attn_gqa.hip: one workgroup per kv head and 64-position split, each cached K / V row loaded
+ * once for the kv head's query heads, q and p as two fp16 planes) wherever head_dim is 128,
+ * 2 <= heads / kv_heads <= 8 (a TP rank: its local counts) and the cache is fp16 or int8; the layer
+ * then takes the q/k/v GEMV, this attention launch and the o_proj. Tokens and logits are faithful
+ * to fp32 but not bitwise option 0's; a run repeats bit for bit, captured or eager. Everywhere else
+ * (MHA, an fp32 cache, a group above 8) and in the ring mode, the verify step and prefill nothing
+ * changes. 0 (default) off; another value is LLMI_EINVAL. */
 int llmi_engine_set_option(llmi_engine* e, const char* name, int value);
 int llmi_engine_set_exchange(llmi_engine* e, int mode);
 /* Diagnostics: kernels launched by llmi_engine_time_kernel (and graphs built
@@ -1276,7 +1291,9 @@ int llmi_batch_load_bin(llmi_batch* b, const char* weight_path);
 int llmi_batch_load_bin_quantized(llmi_batch* b, const char* weight_path);
 int llmi_batch_set_prompt(llmi_batch* b, int seq, const int32_t* ids, int n);
 int llmi_batch_reset(llmi_batch* b, int seq);
-/* Batch options (same-process A/B, as llmi_engine_set_option is for an engine). One name:
+/* Batch options (same-process A/B, as llmi_engine_set_option is for an engine). Two names:
+ *   "gqa_attn" 0 (default) / 1: llmi_engine_set_option's switch of the same name for every slot's
+ * per-sequence attention launch; a slot is then bitwise an engine with the option on.
  *   "rows_mfma" 0 (default) / 1: the q/k/v, gate_up and down projections of a step run on the
  * matrix cores (csrc/gemv_rows_mfma.hip: one launch at every k, x as two fp16 planes) wherever
  * that kernel serves the shape -- fp16 / int8 weights, k a multiple of 32 -- and as before

@@ -198,7 +198,9 @@ int attn_decode_launch(const AttnArgs& a, hipStream_t s) {
     LLMI_REQUIRE(a.nact == 0 || a.pos_dev, "attn: nact > 0 needs the device position");
     const bool hs = a.nact > 0;
     const dim3 grid(a.heads, hs ? a.nact : ns);
-    if (a.cache_dtype == LLMI_F16) {
+    if (a.gqa && attn_gqa_supported(a)) {  // opt-in: one workgroup per (kv head, split), attn_gqa.hip
+        LLMI_TRY(attn_gqa_launch(a, s));
+    } else if (a.cache_dtype == LLMI_F16) {
         if (hs)
             hipLaunchKernelGGL((attn_decode_kernel<__half, true>), grid, dim3(kThreads), kAttnLds, s, a, ns);
         else

@@ -199,6 +199,13 @@ int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t 
     at.hidden = d.n_rows;
     at.err = d.err;
     at.k_scale = static_cast<__half*>(d.k_scale); at.v_scale = static_cast<__half*>(d.v_scale);
+    LLMI_REQUIRE(d.gqa == 0 || d.gqa == 1, "debug_attn_oproj: gqa must be 0 or 1");
+    at.gqa = d.gqa;
+    if (at.gqa && !attn_gqa_supported(at)) {
+        set_last_error("[llmi][ERROR] debug_attn_oproj: gqa 1 serves head_dim 128, 2 <= heads / kv_heads <= 8 and a "
+                       "16-byte aligned f16 or i8 cache");
+        return LLMI_EUNSUPPORTED;
+    }
     OprojArgs o;
     o.w = d.w; o.scales = reinterpret_cast<const __half*>(d.scales); o.w_dtype = d.w_dtype;
     o.head_major = d.head_major; o.n_rows = d.n_rows; o.ldw = d.ldw;

@@ -261,6 +261,9 @@ struct Engine {
     bool qa_o = LLMI_QKV_ATTN_O != 0;  // ... with the o_proj in the same launch (option "qa_o")
     unsigned long long* qtag = nullptr;
     bool kpar_off = false;  // option "kpar" 0
+    // option "gqa_attn" 1: where attn_gqa_supported accepts the layer (GQA, fp16 / int8 cache),
+    // rec_attn takes the unfused route with the grouped-query attention kernel (attn_gqa.hip)
+    bool gqa_attn = false;
 
     // -------------------------------------------------------- TP exchange
     ncclComm_t comm = nullptr;

@@ -162,6 +162,11 @@ int Engine::rec_start() {
 int Engine::rec_attn(int l) {
     GemvArgs q = qkv_args(l);
     AttnArgs at = attn_args(l);
+    at.gqa = gqa_attn;
+    if (at.gqa && attn_gqa_supported(at)) {  // q/k/v GEMV, grouped-query attention, o_proj
+        LLMI_TRY(gemv_launch(q, stream));
+        return rec_oproj(LLMI_OK, o_args(l), &at);
+    }
     if (qa_fuse && qtag && l < 128) {
         GemvArgs qf = q;
         qf.kpar = 0;  // the fused GEMV part streams a row group per wave (kpar: +0.3 % alone at TP 8)
@@ -411,9 +416,13 @@ int Engine::set_option(const std::string& name, int value) {
     } else if (name == "w4_gemm") {
         LLMI_REQUIRE(value == 0 || value == 1, "set_option w4_gemm: 1 int4 prefill on gemm_w4, 0 none (default)");
         w4_gemm = value == 1;
+    } else if (name == "gqa_attn") {
+        LLMI_REQUIRE(value == 0 || value == 1,
+                     "set_option gqa_attn: 1 grouped-query decode attention on the matrix cores, 0 off (default)");
+        gqa_attn = value == 1;
     } else {
-        LLMI_REQUIRE(false,
-                     "set_option: unknown option (kpar, qkv_attn, qa_o, qa_grid, qa_order, qa_poll, w8_gemm, w4_gemm)");
+        LLMI_REQUIRE(false, "set_option: unknown option (kpar, qkv_attn, qa_o, qa_grid, qa_order, qa_poll, w8_gemm, "
+                            "w4_gemm, gqa_attn)");
     }
     return invalidate();
 }

@@ -39,7 +39,13 @@ int Batch::reset(int seq) {
     return LLMI_OK;
 }
 int Batch::set_option(const std::string& name, int value) {
-    LLMI_REQUIRE(name == "rows_mfma", "batch set_option: unknown option (rows_mfma)");
+    LLMI_REQUIRE(name == "rows_mfma" || name == "gqa_attn", "batch set_option: unknown option (rows_mfma, gqa_attn)");
+    if (name == "gqa_attn") {  // every slot's per-sequence attention launch (Engine::gqa_attn)
+        LLMI_REQUIRE(value == 0 || value == 1,
+                     "batch set_option gqa_attn: 1 grouped-query decode attention on the matrix cores, 0 off (default)");
+        for (auto& e : r) e->gqa_attn = value == 1;
+        return graphs.drop(stream);
+    }
     LLMI_REQUIRE(value == 0 || value == 1,
                  "batch set_option rows_mfma: 1 q/k/v, gate_up and down on the matrix cores, 0 off (default)");
     rows_mfma = value != 0;
@@ -83,7 +89,8 @@ int Batch::record_step(const std::vector<int>& act) {
     for (int l = 0; l < L; ++l) {
         LLMI_TRY(proj([&](Engine& e) { return e.qkv_args(l); }));
         for (Engine* e : es) {
-            const AttnArgs at = e->attn_args(l);
+            AttnArgs at = e->attn_args(l);
+            at.gqa = e->gqa_attn;
             LLMI_TRY(e->rec_oproj(LLMI_OK, e->o_args(l), &at));
         }
         LLMI_TRY(proj([&](Engine& e) { return e.gu_args(l); }));

@@ -40,7 +40,11 @@ int llmi_engine_time_kernel(llmi_engine* e, int which, int iters, float* avg_us,
         const int l = li++ % g.c.layers;
         switch (which) {
             case 0: return llmi::gemv_launch(g.qkv_args(l), g.stream);
-            case 1: return llmi::attn_decode_launch(g.attn_args(l), g.stream);
+            case 1: {  // (option "gqa_attn": the grouped-query kernel where it serves the shape)
+                llmi::AttnArgs at = g.attn_args(l);
+                at.gqa = g.gqa_attn;
+                return llmi::attn_decode_launch(at, g.stream);
+            }
             case 2: return llmi::attn_oproj_launch(g.o_args(l), g.stream);
             case 3: return llmi::gemv_launch(g.gu_args(l), g.stream);
             case 4: return llmi::gemv_launch(g.down_args(l), g.stream);

@@ -437,6 +437,10 @@ struct AttnArgs {
     // 1 (the fused launch with its o_proj part): partials stored write-through, then one arrival
     // per workgroup on the head's counter (workspace counters word 0) for the o_proj blocks
     int publish = 0;
+    // 1 (opt-in: engine / batch option "gqa_attn"): where attn_gqa_supported accepts the shape,
+    // attn_decode_launch runs the grouped-query kernel (attn_gqa.hip) -- same partials, cache
+    // write, xacc seed and error bits, faithful to fp32 but not bitwise the scalar kernel's
+    int gqa = 0;
 };
 
 // Merge of the split partials fused into the o_proj, split by head: workgroup
@@ -545,6 +549,12 @@ __host__ __device__ __forceinline__ float from_fixed(long long v) {
 constexpr int kAttnChunk = LLMI_ATTN_CH;  // cached positions per workgroup (split-KV)
 size_t attn_workspace_bytes(int heads, int head_dim, int max_seq);
 int attn_decode_launch(const AttnArgs& a, hipStream_t s);
+// the grouped-query form of the attention kernel (attn_gqa.hip; AttnArgs::gqa): one workgroup per
+// (kv head, split) on the matrix cores. Served: head_dim 128, 2 <= heads / kv_heads <= 8, an fp16
+// or int8 cache (16-byte aligned), no fused q/k/v hand-off. The launch takes the arguments
+// attn_decode_launch has checked and leaves the merge of a direct_out call to it.
+bool attn_gqa_supported(const AttnArgs& a);
+int attn_gqa_launch(const AttnArgs& a, hipStream_t s);
 // the q/k/v GEMV (g: EPI_STORE, rmsnorm, fixed-point x) and the attention (at: host-sized)
 // of one decode layer as ONE launch, q/k/v handed over as tagged granules (qkv_attn.hip)
 bool qkv_attn_supported(const GemvArgs& g, const AttnArgs& at);

@@ -68,7 +68,8 @@ class DebugAttnOprojArgs(C.Structure):
                 ("xacc", C.c_void_p), ("resid", C.c_void_p), ("resid_fixed", C.c_void_p),
                 ("resid_scale", C.c_float), ("w", C.c_void_p), ("scales", C.c_void_p),
                 ("w_dtype", C.c_int), ("head_major", C.c_int), ("n_rows", C.c_int), ("ldw", C.c_int),
-                ("err", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p)]
+                ("err", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
+                ("gqa", C.c_int)]
 
 
 class DebugPrefillAttnArgs(C.Structure):

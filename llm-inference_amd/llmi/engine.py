@@ -356,7 +356,9 @@ class Engine:
         call("llmi_engine_xchg_open", self._h, buf)
 
     def set_option(self, name: str, value: int):
-        """llmi_engine_set_option: tuning switches for same-process A/B ("kpar": 0 / 1)."""
+        """llmi_engine_set_option: tuning switches for same-process A/B ("kpar": 0 / 1);
+        "gqa_attn" 1 runs the decode attention of a GQA model (2 <= heads / kv_heads <= 8, fp16 or
+        int8 cache) as one workgroup per kv head and split on the matrix cores (off by default)."""
         call("llmi_engine_set_option", self._h, name.encode(), int(value))
 
     def xchg_loopback(self):
@@ -582,7 +584,8 @@ class Batch:
         self._plen[int(seq)], self._pos[int(seq)] = 0, 0
 
     def set_option(self, name: str, value: int):
-        """llmi_batch_set_option: "rows_mfma" 1 runs the q/k/v, gate_up and down projections on the
+        """llmi_batch_set_option: "gqa_attn" 0 / 1 is Engine.set_option's switch for every slot's
+        attention launch; "rows_mfma" 1 runs the q/k/v, gate_up and down projections on the
         matrix cores (fp32-faithful and slot-independent, not bitwise the engine's); 0 (default) off."""
         call("llmi_batch_set_option", self._h, name.encode(), int(value))
 
