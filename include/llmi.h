@@ -293,6 +293,18 @@ int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t 
  * order. m outside 2..8: LLMI_EINVAL; an int8 cache: LLMI_EUNSUPPORTED. Nothing is launched on
  * an error. */
 int llmi_debug_attn_oproj_rows(const llmi_debug_attn_oproj_args* args, int m, llmi_stream_t stream);
+/* llmi_debug_attn_oproj_batch: the batched attention + o_proj behind llmi_batch_set_option
+ * "batch_attn" (csrc/attn_batch.hip) -- slots[0 .. n), 1 <= n <= 8, are n UNRELATED sequences,
+ * each block with its own qkv, caches (and int8 scales), pos_dev, nact, workspace, xacc, residual
+ * seed and err: one attention launch over all slots and one o_proj launch that loads W_o once.
+ * The blocks must agree in cache_dtype, max_seq, heads, kv_heads, head_dim, rope, rope_base, w,
+ * scales, w_dtype, head_major, n_rows and ldw (else LLMI_EINVAL). Every slot's nact must be its
+ * host-sized split count *pos_dev / 64 + 1 (0 is refused; a mismatch sets bit 4 in that slot's
+ * *err and computes nothing for it); gqa must be 0; a slot with neither resid nor resid_fixed is
+ * pre-seeded. Slot i's xacc, partials and cache row are bitwise those of
+ * llmi_debug_attn_oproj(&slots[i]), whatever the other slots are. Nothing is launched on an
+ * error. */
+int llmi_debug_attn_oproj_batch(const llmi_debug_attn_oproj_args* slots, int n, llmi_stream_t stream);
 
 /* Diagnostics (no reference counterpart): while `stamps` (device memory, 8 u64 per
  * workgroup) is non-null, every launch of the transposed prefill attention kernel writes its
@@ -1291,7 +1303,12 @@ int llmi_batch_load_bin(llmi_batch* b, const char* weight_path);
 int llmi_batch_load_bin_quantized(llmi_batch* b, const char* weight_path);
 int llmi_batch_set_prompt(llmi_batch* b, int seq, const int32_t* ids, int n);
 int llmi_batch_reset(llmi_batch* b, int seq);
-/* Batch options (same-process A/B, as llmi_engine_set_option is for an engine). Two names:
+/* Batch options (same-process A/B, as llmi_engine_set_option is for an engine). Three names:
+ *   "batch_attn" 0 (default) / 1: with two or more active slots a step runs the slots' attention
+ * as ONE launch and their merge + o_proj as ONE launch per layer (csrc/attn_batch.hip) instead of
+ * one pair per slot, so W_o is streamed once per step. Tokens, logits and cache rows are bitwise
+ * those of 0. One active slot keeps the per-slot launches; with "gqa_attn" 1 as well the
+ * attention stays per slot on the grouped-query kernel and only the o_proj is batched.
  *   "gqa_attn" 0 (default) / 1: llmi_engine_set_option's switch of the same name for every slot's
  * per-sequence attention launch; a slot is then bitwise an engine with the option on.
  *   "rows_mfma" 0 (default) / 1: the q/k/v, gate_up and down projections of a step run on the
@@ -1375,9 +1392,12 @@ int llmi_batch_decode(llmi_batch* b, int n_steps, int use_graph);
 int llmi_batch_prefill(llmi_batch* b, int seq, int n_tokens, int exact, int scored);
 int llmi_batch_tokens(llmi_batch* b, int seq, int32_t* out, int n, int* n_valid);
 int llmi_batch_logits(llmi_batch* b, int seq, float* out, int n);
+/* llmi_engine_kv_slot / llmi_engine_kv_slot_q8 of slot seq's own cache (a slot's stream is the batch's). */
+int llmi_batch_kv_slot(llmi_batch* b, int seq, int layer, int pos, int which_v, float* out);
+int llmi_batch_kv_slot_q8(llmi_batch* b, int seq, int layer, int pos, int which_v, int8_t* q, uint16_t* scale_bits);
 int llmi_batch_sync(llmi_batch* b);
-/* Bytes one step over the currently active slots streams: the weights once, W_o (still read
- * per slot) once per active slot; and the KV bytes per cached position of one slot. */
+/* Bytes one step over the currently active slots streams: the weights once, W_o once per active
+ * slot (option "batch_attn" 1: once); and the KV bytes per cached position of one slot. */
 int llmi_batch_bytes(llmi_batch* b, uint64_t* weight_bytes_per_step, uint64_t* kv_bytes_per_pos);
 
 #ifdef __cplusplus

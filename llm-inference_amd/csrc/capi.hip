@@ -269,6 +269,50 @@ int llmi_debug_attn_oproj_rows(const llmi_debug_attn_oproj_args* args, int m, ll
     return oproj_rows_launch(o, STREAM(stream));
 }
 
+int llmi_debug_attn_oproj_batch(const llmi_debug_attn_oproj_args* slots, int n, llmi_stream_t stream) {
+    LLMI_REQUIRE(slots != nullptr, "debug_attn_oproj_batch: null arguments");
+    LLMI_REQUIRE(n >= 1 && n <= kAttnBatchMax, "debug_attn_oproj_batch: n must be 1..8");
+    const llmi_debug_attn_oproj_args& z = slots[0];
+    LLMI_REQUIRE(z.n_rows > 0, "debug_attn_oproj_batch: n_rows needed");
+    AttnBatchArgs at;
+    OprojBatchArgs o;
+    at.n = o.n = n;
+    for (int i = 0; i < n; ++i) {
+        const llmi_debug_attn_oproj_args& d = slots[i];
+        LLMI_REQUIRE(d.cache_dtype == z.cache_dtype && d.max_seq == z.max_seq && d.heads == z.heads &&
+                         d.kv_heads == z.kv_heads && d.head_dim == z.head_dim && d.rope == z.rope &&
+                         d.rope_base == z.rope_base && d.w == z.w && d.scales == z.scales && d.w_dtype == z.w_dtype &&
+                         d.head_major == z.head_major && d.n_rows == z.n_rows && d.ldw == z.ldw,
+                     "debug_attn_oproj_batch: the slots must share the shapes, cache dtype, rope and W_o");
+        LLMI_REQUIRE(d.pos_dev && d.xacc && d.err, "debug_attn_oproj_batch: a slot's pos_dev, xacc or err is null");
+        LLMI_REQUIRE(d.gqa == 0, "debug_attn_oproj_batch: gqa is a single-sequence field");
+        AttnBatchSlot& r = at.slot[i];
+        r.qkv = d.qkv; r.k_cache = d.k_cache; r.v_cache = d.v_cache;
+        r.k_scale = static_cast<__half*>(d.k_scale); r.v_scale = static_cast<__half*>(d.v_scale);
+        r.pos_dev = d.pos_dev; r.nact = d.nact; r.workspace = d.workspace; r.xacc = d.xacc;
+        r.resid = d.resid; r.resid_fixed = d.resid_fixed; r.resid_scale = d.resid_scale; r.err = d.err;
+        o.slot[i] = r;
+        // neither seed source: xacc is pre-seeded (the engine's form when the down GEMV wrote it)
+        if (!d.resid && !d.resid_fixed) r.xacc = nullptr;
+    }
+    AttnArgs& a = at.a;
+    a.cache_dtype = z.cache_dtype; a.max_seq = z.max_seq;
+    a.heads = z.heads; a.kv_heads = z.kv_heads; a.head_dim = z.head_dim ? z.head_dim : 128;
+    a.rope = z.rope; a.rope_base = z.rope_base != 0.f ? z.rope_base : 10000.f;
+    a.direct_out = 0;
+    a.hidden = z.n_rows;
+    OprojArgs& w = o.a;
+    w.w = z.w; w.scales = reinterpret_cast<const __half*>(z.scales); w.w_dtype = z.w_dtype;
+    w.head_major = z.head_major; w.n_rows = z.n_rows; w.ldw = z.ldw;
+    w.heads = z.heads; w.head_dim = a.head_dim; w.max_seq = z.max_seq;
+    // both argument checks before either launch (as llmi_debug_attn_oproj)
+    LLMI_REQUIRE(w.w && w.ldw >= w.heads * 128 && w.ldw % 16 == 0 && (w.w_dtype != LLMI_I8 || w.scales) &&
+                     (w.w_dtype == LLMI_F16 || w.w_dtype == LLMI_F32 || w.w_dtype == LLMI_I8),
+                 "debug_attn_oproj_batch: bad W_o arguments");
+    LLMI_TRY(attn_batch_launch(at, STREAM(stream)));
+    return oproj_batch_launch(o, STREAM(stream));
+}
+
 int llmi_debug_prefill_stamps(void* stamps) {
     prefill_stamps_debug(static_cast<unsigned long long*>(stamps));
     return LLMI_OK;

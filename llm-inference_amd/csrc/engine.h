@@ -568,7 +568,8 @@ struct Group {
 // gemv_rows_mfma.hip instead, for one active slot too: faithful, slot-independent, not bitwise.)
 // The multi-row GEMV gives every row bitwise the single-row result, and
 // everything else is the engine's own launch, so a slot's tokens and logits are bitwise those
-// of an Engine decoding the sequence alone. W_o is still streamed once per slot. A slot's prompt
+// of an Engine decoding the sequence alone. W_o is streamed once per slot, unless the option
+// "batch_attn" replaces the per-slot launches by attn_batch.hip's two (bitwise the same). A slot's prompt
 // can run through the engine's own (scored) prefill, one slot per call, on slot 0's prefill
 // scratch, e4m3 weight copies and logits slab (Engine::pf_from): once per batch, not per slot.
 struct Batch {
@@ -580,6 +581,9 @@ struct Batch {
     BatchGraphs graphs{kMaxGraphs};
     // set_option "rows_mfma": q/k/v, gate_up and down on gemv_rows_mfma_launch where it serves them
     bool rows_mfma = false;
+    // set_option "batch_attn": with two or more active slots, the slots' attention and merge +
+    // o_proj as ONE launch each per layer (attn_batch.hip): W_o streamed once per step, bitwise
+    bool batch_attn = false;
 
     ~Batch();
     int init(const llmi_config& cfg, int n_seq, int dev);

@@ -39,7 +39,15 @@ int Batch::reset(int seq) {
     return LLMI_OK;
 }
 int Batch::set_option(const std::string& name, int value) {
-    LLMI_REQUIRE(name == "rows_mfma" || name == "gqa_attn", "batch set_option: unknown option (rows_mfma, gqa_attn)");
+    LLMI_REQUIRE(name == "rows_mfma" || name == "gqa_attn" || name == "batch_attn",
+                 "batch set_option: unknown option (rows_mfma, gqa_attn, batch_attn)");
+    if (name == "batch_attn") {  // record_step: the slots' attention and o_proj as two launches a layer
+        LLMI_REQUIRE(value == 0 || value == 1,
+                     "batch set_option batch_attn: 1 one attention and one o_proj launch per layer for all active "
+                     "slots, 0 one pair per slot (default)");
+        batch_attn = value == 1;
+        return graphs.drop(stream);
+    }
     if (name == "gqa_attn") {  // every slot's per-sequence attention launch (Engine::gqa_attn)
         LLMI_REQUIRE(value == 0 || value == 1,
                      "batch set_option gqa_attn: 1 grouped-query decode attention on the matrix cores, 0 off (default)");
@@ -86,12 +94,34 @@ int Batch::record_step(const std::vector<int>& act) {
         if (gemv_rows_mfma_supported(p)) return gemv_rows_mfma_launch(p, stream);
         return p.m == 1 ? gemv_launch(args_of(*es[0]), stream) : rows(args_of);
     };
-    for (int l = 0; l < L; ++l) {
-        LLMI_TRY(proj([&](Engine& e) { return e.qkv_args(l); }));
+    // option batch_attn, two or more slots: ONE attention launch and ONE o_proj launch for all of
+    // them (attn_batch.hip), from each slot's own single-sequence arguments. With gqa_attn on as
+    // well the attention stays per slot on the grouped-query kernel where it serves the shape
+    // (the same workspace format) and only the o_proj is batched.
+    auto attn_batched = [&](int l) -> int {
+        AttnBatchArgs ab;
+        OprojBatchArgs ob;
         for (Engine* e : es) {
             AttnArgs at = e->attn_args(l);
             at.gqa = e->gqa_attn;
-            LLMI_TRY(e->rec_oproj(LLMI_OK, e->o_args(l), &at));
+            if (at.gqa && attn_gqa_supported(at)) LLMI_TRY(attn_decode_launch(at, stream));
+            else attn_batch_add(ab, at);
+            oproj_batch_add(ob, e->o_args(l));
+        }
+        ab.a.stamps = ob.a.stamps = nullptr;  // (debug stamps: a single-sequence form)
+        if (ab.n) LLMI_TRY(attn_batch_launch(ab, stream));
+        return oproj_batch_launch(ob, stream);
+    };
+    for (int l = 0; l < L; ++l) {
+        LLMI_TRY(proj([&](Engine& e) { return e.qkv_args(l); }));
+        if (batch_attn && es.size() >= 2) {
+            LLMI_TRY(attn_batched(l));
+        } else {
+            for (Engine* e : es) {
+                AttnArgs at = e->attn_args(l);
+                at.gqa = e->gqa_attn;
+                LLMI_TRY(e->rec_oproj(LLMI_OK, e->o_args(l), &at));
+            }
         }
         LLMI_TRY(proj([&](Engine& e) { return e.gu_args(l); }));
         LLMI_TRY(proj([&](Engine& e) { return e.down_args(l); }));

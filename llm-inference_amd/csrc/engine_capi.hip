@@ -281,9 +281,8 @@ int llmi_engine_hidden(llmi_engine* e, float* out, int n) {
     return LLMI_OK;
 }
 
-int llmi_engine_kv_slot(llmi_engine* e, int layer, int pos, int which_v, float* out) {
-    LLMI_REQUIRE(e && out, "kv_slot: null argument");
-    Engine& g = e->e;
+// (an engine's, or a batch slot's: llmi_batch_kv_slot)
+static int kv_slot_of(Engine& g, int layer, int pos, int which_v, float* out) {
     LLMI_REQUIRE(layer >= 0 && layer < g.c.layers && pos >= 0 && pos < g.c.max_seq, "kv_slot: out of range");
     LLMI_HIP(hipStreamSynchronize(g.stream));
     const size_t eb = llmi::dtype_size(g.c.kv_dtype), D = g.c.head_dim;
@@ -311,9 +310,12 @@ int llmi_engine_kv_slot(llmi_engine* e, int layer, int pos, int which_v, float* 
     return LLMI_OK;
 }
 
-int llmi_engine_kv_slot_q8(llmi_engine* e, int layer, int pos, int which_v, int8_t* q, uint16_t* scale_bits) {
-    LLMI_REQUIRE(e && q && scale_bits, "kv_slot_q8: null argument");
-    Engine& g = e->e;
+int llmi_engine_kv_slot(llmi_engine* e, int layer, int pos, int which_v, float* out) {
+    LLMI_REQUIRE(e && out, "kv_slot: null argument");
+    return kv_slot_of(e->e, layer, pos, which_v, out);
+}
+
+static int kv_slot_q8_of(Engine& g, int layer, int pos, int which_v, int8_t* q, uint16_t* scale_bits) {
     LLMI_REQUIRE(g.c.kv_dtype == LLMI_I8, "kv_slot_q8: the engine's KV cache is not int8");
     LLMI_REQUIRE(layer >= 0 && layer < g.c.layers && pos >= 0 && pos < g.c.max_seq, "kv_slot_q8: out of range");
     LLMI_HIP(hipStreamSynchronize(g.stream));
@@ -323,6 +325,11 @@ int llmi_engine_kv_slot_q8(llmi_engine* e, int layer, int pos, int which_v, int8
     LLMI_HIP(hipMemcpy2D(scale_bits, 2, g.kv_scale_layer(layer, which_v) + pos, (size_t)g.c.max_seq * 2, 2, g.kvl,
                          hipMemcpyDeviceToHost));
     return LLMI_OK;
+}
+
+int llmi_engine_kv_slot_q8(llmi_engine* e, int layer, int pos, int which_v, int8_t* q, uint16_t* scale_bits) {
+    LLMI_REQUIRE(e && q && scale_bits, "kv_slot_q8: null argument");
+    return kv_slot_q8_of(e->e, layer, pos, which_v, q, scale_bits);
 }
 
 int llmi_engine_bytes(llmi_engine* e, uint64_t* weight_bytes, uint64_t* kv_bytes_per_pos) {
@@ -689,6 +696,18 @@ int llmi_batch_logits(llmi_batch* b, int seq, float* out, int n) {
     return LLMI_OK;
 }
 
+int llmi_batch_kv_slot(llmi_batch* b, int seq, int layer, int pos, int which_v, float* out) {
+    LLMI_REQUIRE(b && out, "batch_kv_slot: null argument");
+    LLMI_TRY(b->b.slot_ok(seq));
+    return kv_slot_of(*b->b.r[seq], layer, pos, which_v, out);
+}
+
+int llmi_batch_kv_slot_q8(llmi_batch* b, int seq, int layer, int pos, int which_v, int8_t* q, uint16_t* scale_bits) {
+    LLMI_REQUIRE(b && q && scale_bits, "batch_kv_slot_q8: null argument");
+    LLMI_TRY(b->b.slot_ok(seq));
+    return kv_slot_q8_of(*b->b.r[seq], layer, pos, which_v, q, scale_bits);
+}
+
 int llmi_batch_sync(llmi_batch* b) {
     LLMI_REQUIRE(b, "null batch");
     LLMI_HIP(hipStreamSynchronize(b->b.stream));
@@ -699,10 +718,12 @@ int llmi_batch_bytes(llmi_batch* b, uint64_t* weight_bytes_per_step, uint64_t* k
     LLMI_REQUIRE(b, "null batch");
     const Engine& g = *b->b.r[0];
     const uint64_t n_act = b->b.active().size();
-    // the weights once; W_o (+ its int8 row scales) once more for every further active slot
+    // the weights once; W_o (+ its int8 row scales) once more for every further active slot --
+    // unless the option "batch_attn" runs the slots' o_proj as one launch
     const uint64_t wo = Engine::lin_bytes(g.odt(), g.c.hidden, g.ql) + Engine::scale_bytes(g.odt(), g.c.hidden, g.ql);
     if (weight_bytes_per_step)
-        *weight_bytes_per_step = g.stream_bytes + (n_act > 1 ? (n_act - 1) * wo * g.c.layers : 0);
+        *weight_bytes_per_step =
+            g.stream_bytes + (n_act > 1 && !b->b.batch_attn ? (n_act - 1) * wo * g.c.layers : 0);
     if (kv_bytes_per_pos)
         *kv_bytes_per_pos = (uint64_t)g.c.layers * g.kvl * 2 *  // (int8 rows carry an fp16 scale)
                             (g.c.head_dim * llmi::dtype_size(g.c.kv_dtype) + (g.c.kv_dtype == LLMI_I8 ? 2 : 0));

@@ -497,6 +497,57 @@ struct OprojRowsArgs {
 int attn_rows_launch(const AttnRowsArgs& p, hipStream_t s);
 int oproj_rows_launch(const OprojRowsArgs& p, hipStream_t s);
 
+// ------------------- batched decode attention + o_proj over sequence slots (attn_batch.hip)
+// n = 1..kAttnBatchMax sequences that share nothing but the shapes and W_o: every slot has its
+// own q/k/v row, cache, position, host-sized split count, workspace, xacc and error word. ONE
+// attention launch (grid (heads, max nact, n): blockIdx.z is the slot, a workgroup past its
+// slot's nact leaves at once) and ONE o_proj launch whose workgroups hold their W_o slice in
+// registers while they walk the slots. Slot s's cache row, partials and xacc are bitwise those of
+// attn_decode_launch + attn_oproj_launch for slot s alone, whatever the other slots are.
+constexpr int kAttnBatchMax = 8;
+struct AttnBatchSlot {  // what differs between the slots (AttnArgs' / OprojArgs' fields of the same names)
+    const float* qkv = nullptr;
+    void* k_cache = nullptr;
+    void* v_cache = nullptr;
+    __half* k_scale = nullptr;
+    __half* v_scale = nullptr;
+    const int* pos_dev = nullptr;
+    int nact = 0;  // > 0: the slot's position is tracked on the host (the only form served)
+    void* workspace = nullptr;
+    long long* xacc = nullptr;  // attention: the seed target (null: seeded already); o_proj: the sum
+    const float* resid = nullptr;
+    const long long* resid_fixed = nullptr;
+    float resid_scale = 1.f;
+    int* err = nullptr;
+};
+struct AttnBatchArgs {
+    AttnArgs a;  // shapes, max_seq, rope, cache dtype, hidden; its per-slot fields are unused
+    int n = 0;
+    AttnBatchSlot slot[kAttnBatchMax];
+};
+struct OprojBatchArgs {
+    OprojArgs a;  // W_o, its scales and layout, shapes; its per-slot fields are unused
+    int n = 0;
+    AttnBatchSlot slot[kAttnBatchMax];  // nact, workspace and xacc used
+};
+// append the slot of the single-sequence arguments r (the first slot's also become p.a)
+inline void attn_batch_add(AttnBatchArgs& p, const AttnArgs& r) {
+    if (p.n == 0) p.a = r;
+    AttnBatchSlot& w = p.slot[p.n++];
+    w.qkv = r.qkv; w.k_cache = r.k_cache; w.v_cache = r.v_cache; w.k_scale = r.k_scale; w.v_scale = r.v_scale;
+    w.pos_dev = r.pos_dev; w.nact = r.nact; w.workspace = r.workspace; w.xacc = r.xacc;
+    w.resid = r.resid; w.resid_fixed = r.resid_fixed; w.resid_scale = r.resid_scale; w.err = r.err;
+}
+inline void oproj_batch_add(OprojBatchArgs& p, const OprojArgs& r) {
+    if (p.n == 0) p.a = r;
+    AttnBatchSlot& w = p.slot[p.n++];
+    w.nact = r.nact; w.workspace = const_cast<void*>(r.workspace); w.xacc = r.xacc;
+}
+// LLMI_EUNSUPPORTED: the merged output form (direct_out), granule rows (qkv_tag, publish), a
+// fused exchange tail, stamps. LLMI_EINVAL: n outside 1..8, a slot without a host-sized nact.
+int attn_batch_launch(const AttnBatchArgs& p, hipStream_t s);
+int oproj_batch_launch(const OprojBatchArgs& p, hipStream_t s);
+
 // Persistent ring layer (ring.hip): after layer l's attention, ONE launch runs
 //   o_proj (merge fused, by head) -> RMSNorm + gate_up + SiLU*up -> down (K split by CU)
 //   -> [RMSNorm + next layer's q/k/v]

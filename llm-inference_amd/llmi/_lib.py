@@ -162,6 +162,7 @@ _SIGS = {
     "llmi_debug_gemv_plan": (_I, [C.POINTER(DebugGemvArgs), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "llmi_debug_attn_oproj": (_I, [C.POINTER(DebugAttnOprojArgs), _P]),
     "llmi_debug_attn_oproj_rows": (_I, [C.POINTER(DebugAttnOprojArgs), _I, _P]),
+    "llmi_debug_attn_oproj_batch": (_I, [C.POINTER(DebugAttnOprojArgs), _I, _P]),
     "llmi_debug_prefill_stamps": (_I, [_P]),
     "llmi_debug_prefill_attn": (_I, [C.POINTER(DebugPrefillAttnArgs), _P]),
     "llmi_debug_prefill_attn_plan": (_I, [C.POINTER(DebugPrefillAttnArgs), C.POINTER(_I), C.POINTER(_I),
@@ -271,6 +272,8 @@ _SIGS = {
     "llmi_batch_prefill": (_I, [_P, _I, _I, _I, _I]),
     "llmi_batch_tokens": (_I, [_P, _I, _P, _I, C.POINTER(_I)]),
     "llmi_batch_logits": (_I, [_P, _I, _P, _I]),
+    "llmi_batch_kv_slot": (_I, [_P, _I, _I, _I, _I, _P]),
+    "llmi_batch_kv_slot_q8": (_I, [_P, _I, _I, _I, _I, _P, _P]),
     "llmi_batch_sync": (_I, [_P]),
     "llmi_batch_bytes": (_I, [_P, C.POINTER(_U64), C.POINTER(_U64)]),
 }

@@ -586,7 +586,9 @@ class Batch:
     def set_option(self, name: str, value: int):
         """llmi_batch_set_option: "gqa_attn" 0 / 1 is Engine.set_option's switch for every slot's
         attention launch; "rows_mfma" 1 runs the q/k/v, gate_up and down projections on the
-        matrix cores (fp32-faithful and slot-independent, not bitwise the engine's); 0 (default) off."""
+        matrix cores (fp32-faithful and slot-independent, not bitwise the engine's); "batch_attn" 1
+        runs the active slots' attention and their merge + o_proj as one launch each per layer
+        (W_o streamed once per step; bitwise the per-slot launches); 0 (default) off."""
         call("llmi_batch_set_option", self._h, name.encode(), int(value))
 
     def edit(self, seq: int, keep: int, ids):
@@ -761,8 +763,22 @@ class Batch:
         call("llmi_batch_logits", self._h, int(seq), out.ctypes.data, self.cfg.vocab)
         return out
 
+    def kv_slot(self, seq: int, layer: int, pos: int, which_v: bool = False) -> np.ndarray:
+        """Engine.kv_slot of slot seq's own cache."""
+        out = np.zeros((self.cfg.kv_heads, self.cfg.head_dim), np.float32)
+        call("llmi_batch_kv_slot", self._h, int(seq), layer, pos, 1 if which_v else 0, out.ctypes.data)
+        return out
+
+    def kv_slot_q8(self, seq: int, layer: int, pos: int, which_v: bool = False):
+        """Engine.kv_slot_q8 of slot seq's own (int8) cache."""
+        q = np.zeros((self.cfg.kv_heads, self.cfg.head_dim), np.int8)
+        s = np.zeros(self.cfg.kv_heads, np.uint16)
+        call("llmi_batch_kv_slot_q8", self._h, int(seq), layer, pos, 1 if which_v else 0, q.ctypes.data, s.ctypes.data)
+        return q, s
+
     def bytes_per_step(self):
-        """(weight bytes one step over the active slots streams, KV bytes per position and slot)."""
+        """(weight bytes one step over the active slots streams -- W_o once per active slot, or once
+        with the option "batch_attn" --, KV bytes per position and slot)."""
         w, kv = C.c_uint64(), C.c_uint64()
         call("llmi_batch_bytes", self._h, C.byref(w), C.byref(kv))
         return w.value, kv.value

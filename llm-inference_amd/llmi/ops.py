@@ -638,6 +638,20 @@ def attn_oproj_rows(rows) -> None:
     call("llmi_debug_attn_oproj_rows", arr, len(rows), _stream())
 
 
+def debug_attn_oproj_batch(slots) -> None:
+    """llmi_debug_attn_oproj_batch (test hook): ONE attention launch and ONE o_proj launch for the
+    unrelated sequences in `slots` (1..8), a list of debug_attn_oproj keyword dicts that share the
+    shapes, cache dtype, rope and W_o and differ in everything else (qkv, caches, pos_dev, nact,
+    workspace, xacc, residual seed, err). Slot i's xacc, partials and cache row are bitwise
+    debug_attn_oproj(**slots[i])'s, whatever the other slots are."""
+    arr = (_lib.DebugAttnOprojArgs * max(len(slots), 1))()
+    for i, fields in enumerate(slots):
+        fields = dict(fields)
+        fields.setdefault("resid_scale", 1.0)
+        arr[i] = _debug_args(_lib.DebugAttnOprojArgs, fields)
+    call("llmi_debug_attn_oproj_batch", arr, len(slots), _stream())
+
+
 def debug_prefill_attn(**fields) -> None:
     """llmi_debug_prefill_attn (test hook): one launch of the prefill attention (rope + cache
     write, attention, merge) with llmi_debug_prefill_attn_args filled from the keywords
