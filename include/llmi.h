@@ -276,6 +276,9 @@ typedef struct llmi_debug_attn_oproj_args {
     void* k_scale; /* cache_dtype LLMI_I8 (KV8): the layer's fp16 row scales [kv_heads, max_seq]; */
     void* v_scale; /* NULL: unused (an f16 / f32 cache) */
     int gqa;       /* 1: the attention launch is the grouped-query kernel (csrc/attn_gqa.hip), see above */
+    /* llmi_debug_attn_oproj_batch only (the other entry points ignore them): the slot's fork group,
+     * 0 = none, and the leading cache rows it shares with that group (csrc/attn_prefix.hip) */
+    int prefix_group, prefix_rows;
 } llmi_debug_attn_oproj_args;
 int llmi_debug_attn_oproj(const llmi_debug_attn_oproj_args* args, llmi_stream_t stream);
 /* llmi_debug_attn_oproj_rows: the multi-row attention + o_proj of a speculative verify step --
@@ -303,7 +306,16 @@ int llmi_debug_attn_oproj_rows(const llmi_debug_attn_oproj_args* args, int m, ll
  * *err and computes nothing for it); gqa must be 0; a slot with neither resid nor resid_fixed is
  * pre-seeded. Slot i's xacc, partials and cache row are bitwise those of
  * llmi_debug_attn_oproj(&slots[i]), whatever the other slots are. Nothing is launched on an
- * error. */
+ * error.
+ * When any slot has prefix_group != 0 the attention launch is the one behind the batch option
+ * "prefix_attn" (csrc/attn_prefix.hip): the slots with the same prefix_group must hold bitwise
+ * equal cache rows [0, prefix_rows) (and scales), and the first P = min(prefix_rows) / 64 * 64 of
+ * them are read once, from the lowest-numbered slot of the group, for all its slots -- the other
+ * slots' copies of those rows are never loaded. A group is served with an f16 / i8 cache, head_dim
+ * 128, heads / kv_heads <= 8, two or more slots and P >= 64 (P is cut to (nact - 1) * 64); the slots
+ * of any other group run as with prefix_group 0. A served slot's xacc and prefix partials are
+ * faithful to fp32 (4e-6 rel-L2), not bitwise; its cache row, its partials of the splits from
+ * P / 64 on and its error word are bitwise those of prefix_group 0. */
 int llmi_debug_attn_oproj_batch(const llmi_debug_attn_oproj_args* slots, int n, llmi_stream_t stream);
 
 /* Diagnostics (no reference counterpart): while `stamps` (device memory, 8 u64 per
@@ -1303,7 +1315,17 @@ int llmi_batch_load_bin(llmi_batch* b, const char* weight_path);
 int llmi_batch_load_bin_quantized(llmi_batch* b, const char* weight_path);
 int llmi_batch_set_prompt(llmi_batch* b, int seq, const int32_t* ids, int n);
 int llmi_batch_reset(llmi_batch* b, int seq);
-/* Batch options (same-process A/B, as llmi_engine_set_option is for an engine). Three names:
+/* Batch options (same-process A/B, as llmi_engine_set_option is for an engine). Four names:
+ *   "prefix_attn" 0 (default) / 1: slots that llmi_batch_fork made of one sequence form a fork
+ * group -- each holds, in its own cache, bitwise the same leading rows (the fork's keep, lowered by
+ * a later llmi_batch_edit; llmi_batch_set_prompt, llmi_batch_reset and a weight load leave the
+ * group). With 1 and two or more active slots a layer's attention is ONE launch
+ * (csrc/attn_prefix.hip) in which the members of a group read its first P = min(shared rows) / 64
+ * * 64 rows once, from one member, on the matrix cores, plus ONE merge + o_proj launch, whatever
+ * "batch_attn" is. Served: an fp16 or int8 cache, head_dim 128, heads / kv_heads <= 8, a group of
+ * two or more active slots with P >= 64; every other slot runs as under "batch_attn" 1 (bitwise).
+ * A served slot's tokens and logits are faithful to fp32, not bitwise option 0's; a run repeats
+ * bit for bit, captured or eager.
  *   "batch_attn" 0 (default) / 1: with two or more active slots a step runs the slots' attention
  * as ONE launch and their merge + o_proj as ONE launch per layer (csrc/attn_batch.hip) instead of
  * one pair per slot, so W_o is streamed once per step. Tokens, logits and cache rows are bitwise

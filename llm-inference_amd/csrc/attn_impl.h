@@ -218,6 +218,8 @@ constexpr size_t kAttnLds = (3 * D + CH + (kThreads / LPR) * D + 4) * sizeof(flo
 // loads are issued from the kernel arguments alone, before the device position (a
 // scalar load from memory another kernel just wrote) has arrived; rows past the
 // position are loaded (valid cache memory below max_seq) and ignored.
+// first: the lowest split this launch runs attn_body for (0 everywhere but behind a shared
+// prefix, attn_prefix.hip): that split's workgroups seed xacc and report a split-count mismatch.
 // agent-scope (sc1: L1 bypassed) 8-byte granule load, the fused q/k/v launch's hand-off
 __device__ __forceinline__ unsigned long long ld_granule(const unsigned long long* p) {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -230,7 +232,7 @@ __device__ __forceinline__ unsigned long long ld_granule(const unsigned long lon
 // layer's tag; the K/V rows are in flight meanwhile.
 template <typename KT, typename IO, bool HOST_SIZED = false, bool TAGGED = false>
 __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, int ns, float* smem,
-                                          const WgStamp* ts = nullptr) {
+                                          const WgStamp* ts = nullptr, int first = 0) {
     static_assert(!TAGGED || HOST_SIZED, "the fused launch sizes the attention grid on the host");
     static_assert(!TAGGED || !kQ8<KT>, "the fused q/k/v launch takes no int8 cache (qkv_attn_supported)");
     float* q_s = smem;
@@ -316,7 +318,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, i
         pk1 = IO::ld(krow + i + D / 2);
         pv = IO::ld(vrow + (tid & (D - 1)));
         }
-        if (a.xacc != nullptr && split == 0 && a.resid_fixed != nullptr)
+        if (a.xacc != nullptr && split == first && a.resid_fixed != nullptr)
             psd = a.resid_fixed[min(h * seed_per + tid, a.hidden - 1)];
     } else {
         pos = a.pos_dev ? *a.pos_dev : a.pos_host;
@@ -337,7 +339,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, i
         // device state disagrees, keys past nact * CH would be dropped or stale partials
         // merged -- report it (tokens_out raises) instead of computing a wrong token
         if (pos / CH + 1 != a.nact) {
-            if (a.err != nullptr && tid == 0 && split == 0) atomicOr(a.err, 4);
+            if (a.err != nullptr && tid == 0 && split == first) atomicOr(a.err, 4);
             arrive_on_error();
             return;
         }
@@ -563,7 +565,7 @@ __device__ __forceinline__ void attn_body(const AttnArgs& a, int h, int split, i
     // engine path: split 0 of head h seeds the fixed-point residual accumulator of
     // the next kernel (attn_oproj) with its 128-element slice: fixed(resid) on the
     // rank that carries the residual (TP rank 0), zero elsewhere
-    if (a.xacc != nullptr && split == 0) {
+    if (a.xacc != nullptr && split == first) {
         const int per = seed_per;
         for (int i = h * per + tid; i < min((h + 1) * per, a.hidden); i += kThreads) {
             const bool pre = HOST_SIZED && a.resid_fixed && i == h * per + (int)tid;  // prefetched in the prologue

@@ -274,11 +274,17 @@ int llmi_debug_attn_oproj_batch(const llmi_debug_attn_oproj_args* slots, int n, 
     LLMI_REQUIRE(n >= 1 && n <= kAttnBatchMax, "debug_attn_oproj_batch: n must be 1..8");
     const llmi_debug_attn_oproj_args& z = slots[0];
     LLMI_REQUIRE(z.n_rows > 0, "debug_attn_oproj_batch: n_rows needed");
-    AttnBatchArgs at;
+    AttnPrefixArgs px;  // (used when a slot names a fork group)
+    AttnBatchArgs& at = px.b;
     OprojBatchArgs o;
     at.n = o.n = n;
+    bool grouped = false;
     for (int i = 0; i < n; ++i) {
         const llmi_debug_attn_oproj_args& d = slots[i];
+        LLMI_REQUIRE(d.prefix_group >= 0 && d.prefix_rows >= 0, "debug_attn_oproj_batch: prefix_group and prefix_rows must be >= 0");
+        px.group[i] = d.prefix_group;
+        px.rows[i] = d.prefix_rows;
+        grouped = grouped || d.prefix_group != 0;
         LLMI_REQUIRE(d.cache_dtype == z.cache_dtype && d.max_seq == z.max_seq && d.heads == z.heads &&
                          d.kv_heads == z.kv_heads && d.head_dim == z.head_dim && d.rope == z.rope &&
                          d.rope_base == z.rope_base && d.w == z.w && d.scales == z.scales && d.w_dtype == z.w_dtype &&
@@ -309,7 +315,8 @@ int llmi_debug_attn_oproj_batch(const llmi_debug_attn_oproj_args* slots, int n, 
     LLMI_REQUIRE(w.w && w.ldw >= w.heads * 128 && w.ldw % 16 == 0 && (w.w_dtype != LLMI_I8 || w.scales) &&
                      (w.w_dtype == LLMI_F16 || w.w_dtype == LLMI_F32 || w.w_dtype == LLMI_I8),
                  "debug_attn_oproj_batch: bad W_o arguments");
-    LLMI_TRY(attn_batch_launch(at, STREAM(stream)));
+    if (grouped) LLMI_TRY(attn_prefix_launch(px, STREAM(stream)));
+    else LLMI_TRY(attn_batch_launch(at, STREAM(stream)));
     return oproj_batch_launch(o, STREAM(stream));
 }
 

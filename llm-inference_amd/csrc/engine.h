@@ -264,6 +264,12 @@ struct Engine {
     // option "gqa_attn" 1: where attn_gqa_supported accepts the layer (GQA, fp16 / int8 cache),
     // rec_attn takes the unfused route with the grouped-query attention kernel (attn_gqa.hip)
     bool gqa_attn = false;
+    // a batch slot (host fields, meaningful only inside a Batch): the fork group it belongs to
+    // (0: none) and how many leading cache rows it shares with that group -- every member holds
+    // bitwise the same rows [0, pfx_rows) in its own cache (Batch::fork copies them), so whichever
+    // member the option "prefix_attn" reads them from, and leaving a group, is always right.
+    // set_prompt clears both, edit(keep) lowers pfx_rows to keep; decode and prefill only append.
+    int pfx_group = 0, pfx_rows = 0;
 
     // -------------------------------------------------------- TP exchange
     ncclComm_t comm = nullptr;
@@ -569,7 +575,9 @@ struct Group {
 // The multi-row GEMV gives every row bitwise the single-row result, and
 // everything else is the engine's own launch, so a slot's tokens and logits are bitwise those
 // of an Engine decoding the sequence alone. W_o is streamed once per slot, unless the option
-// "batch_attn" replaces the per-slot launches by attn_batch.hip's two (bitwise the same). A slot's prompt
+// "batch_attn" replaces the per-slot launches by attn_batch.hip's two (bitwise the same), or the option
+// "prefix_attn" by attn_prefix.hip's attention launch and the same o_proj launch: slots forked from one
+// sequence then read the cache rows they share once a step (faithful to fp32, not bitwise). A slot's prompt
 // can run through the engine's own (scored) prefill, one slot per call, on slot 0's prefill
 // scratch, e4m3 weight copies and logits slab (Engine::pf_from): once per batch, not per slot.
 struct Batch {
@@ -584,6 +592,13 @@ struct Batch {
     // set_option "batch_attn": with two or more active slots, the slots' attention and merge +
     // o_proj as ONE launch each per layer (attn_batch.hip): W_o streamed once per step, bitwise
     bool batch_attn = false;
+    // set_option "prefix_attn": with two or more active slots, the attention of a layer is ONE
+    // attn_prefix_launch (attn_prefix.hip: the members of a fork group read the group's shared
+    // leading rows once, from one member) and ONE oproj_batch_launch, whatever batch_attn is; a
+    // slot outside a served group is attn_batch.hip's (with gqa_attn: its own grouped-query launch).
+    // Faithful to fp32, not bitwise the per-slot launches, for the members of a served group.
+    bool prefix_attn = false;
+    int next_group = 1;  // fork group ids (Engine::pfx_group)
 
     ~Batch();
     int init(const llmi_config& cfg, int n_seq, int dev);
@@ -596,6 +611,8 @@ struct Batch {
     int decode(int n, int use_graph);
     int prefill(int seq, int n, int split, bool scored);
     int fork(int src, const int* dst, int n_dst, int keep, const int32_t* ids, int n);  // engine_fork.hip
+    // option prefix_attn: layer l's attention arguments of the active slots with their groups
+    AttnPrefixArgs prefix_args(const std::vector<int>& act, int l);
 };
 
 }  // namespace llmi

@@ -695,6 +695,7 @@ int Engine::set_prompt(const int32_t* ids, int n) {
     if (lp_buf) LLMI_HIP(hipMemsetAsync(lp_buf, 0xFF, lp_bytes(), stream));  // NaN / id -1: not computed
     LLMI_HIP(hipStreamSynchronize(stream));
     host_next_pos = 0;
+    pfx_group = pfx_rows = 0;  // (a batch slot leaves its fork group)
     prompt_len = n;
     sc_m = 0;  // the logits slab holds no row of this prompt
     return LLMI_OK;

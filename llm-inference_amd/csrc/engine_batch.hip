@@ -29,6 +29,7 @@ int Batch::slot_ok(int seq) const {
 }
 int Batch::loaded() {  // slot 0 holds the weights every slot reads
     for (size_t i = 1; i < r.size(); ++i) r[i]->seed = r[0]->seed;
+    for (auto& e : r) e->pfx_group = e->pfx_rows = 0;
     return graphs.drop(stream);
 }
 int Batch::reset(int seq) {
@@ -36,11 +37,19 @@ int Batch::reset(int seq) {
     LLMI_HIP(hipStreamSynchronize(stream));
     r[seq]->prompt_len = 0;
     r[seq]->host_next_pos = 0;
+    r[seq]->pfx_group = r[seq]->pfx_rows = 0;
     return LLMI_OK;
 }
 int Batch::set_option(const std::string& name, int value) {
-    LLMI_REQUIRE(name == "rows_mfma" || name == "gqa_attn" || name == "batch_attn",
-                 "batch set_option: unknown option (rows_mfma, gqa_attn, batch_attn)");
+    LLMI_REQUIRE(name == "rows_mfma" || name == "gqa_attn" || name == "batch_attn" || name == "prefix_attn",
+                 "batch set_option: unknown option (rows_mfma, gqa_attn, batch_attn, prefix_attn)");
+    if (name == "prefix_attn") {  // record_step: forked slots read their shared leading rows once
+        LLMI_REQUIRE(value == 0 || value == 1,
+                     "batch set_option prefix_attn: 1 the slots of a fork group read the cache rows they share once per "
+                     "step (one attention and one o_proj launch per layer), 0 off (default)");
+        prefix_attn = value == 1;
+        return graphs.drop(stream);
+    }
     if (name == "batch_attn") {  // record_step: the slots' attention and o_proj as two launches a layer
         LLMI_REQUIRE(value == 0 || value == 1,
                      "batch set_option batch_attn: 1 one attention and one o_proj launch per layer for all active "
@@ -64,6 +73,16 @@ std::vector<int> Batch::active() const {
     for (int i = 0; i < (int)r.size(); ++i)
         if (r[i]->prompt_len > 0) a.push_back(i);
     return a;
+}
+
+AttnPrefixArgs Batch::prefix_args(const std::vector<int>& act, int l) {
+    AttnPrefixArgs p;
+    for (int s : act) {
+        p.group[p.b.n] = r[s]->pfx_group;
+        p.rows[p.b.n] = r[s]->pfx_rows;
+        attn_batch_add(p.b, r[s]->attn_args(l));
+    }
+    return p;
 }
 
 // one step of the active slots; every slot's rec_nact is set
@@ -112,9 +131,35 @@ int Batch::record_step(const std::vector<int>& act) {
         if (ab.n) LLMI_TRY(attn_batch_launch(ab, stream));
         return oproj_batch_launch(ob, stream);
     };
+    // option prefix_attn, two or more slots: attn_batched's structure with the attention launch
+    // of attn_prefix.hip -- the members of a served fork group read their shared rows once; a
+    // slot in no served group is a slot of attn_batch.hip inside the same launch, or, with
+    // gqa_attn on, its own grouped-query launch as above.
+    auto attn_prefixed = [&](int l) -> int {
+        AttnPrefixArgs all = prefix_args(act, l), pa;
+        const AttnPrefixPlan pl = attn_prefix_plan(all);
+        OprojBatchArgs ob;
+        for (size_t i = 0; i < es.size(); ++i) {
+            AttnArgs at = es[i]->attn_args(l);
+            at.gqa = es[i]->gqa_attn;
+            if (pl.skip[i] == 0 && at.gqa && attn_gqa_supported(at)) {
+                LLMI_TRY(attn_decode_launch(at, stream));
+            } else {
+                pa.group[pa.b.n] = all.group[i];
+                pa.rows[pa.b.n] = all.rows[i];
+                attn_batch_add(pa.b, at);
+            }
+            oproj_batch_add(ob, es[i]->o_args(l));
+        }
+        pa.b.a.stamps = ob.a.stamps = nullptr;  // (debug stamps: a single-sequence form)
+        if (pa.b.n) LLMI_TRY(attn_prefix_launch(pa, stream));
+        return oproj_batch_launch(ob, stream);
+    };
     for (int l = 0; l < L; ++l) {
         LLMI_TRY(proj([&](Engine& e) { return e.qkv_args(l); }));
-        if (batch_attn && es.size() >= 2) {
+        if (prefix_attn && es.size() >= 2) {
+            LLMI_TRY(attn_prefixed(l));
+        } else if (batch_attn && es.size() >= 2) {
             LLMI_TRY(attn_batched(l));
         } else {
             for (Engine* e : es) {
@@ -144,6 +189,15 @@ int Batch::decode(int n, int use_graph) {
             r[s]->rec_nact = Engine::nact_of(r[s]->host_next_pos + i);
             key.push_back(s);
             key.push_back(r[s]->rec_nact);
+        }
+        // option prefix_attn: the plan is part of the step and a fork changes it without dropping
+        // the captured steps, so every slot's (leader, P / 64) is part of the key
+        if (prefix_attn && act.size() >= 2) {
+            const AttnPrefixPlan pl = attn_prefix_plan(prefix_args(act, 0));
+            for (size_t k = 0; k < act.size(); ++k) {
+                key.push_back(act[pl.leader[k]]);
+                key.push_back(pl.skip[k]);
+            }
         }
         if (!use_graph) {
             LLMI_TRY(record_step(act));

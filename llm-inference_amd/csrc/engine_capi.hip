@@ -719,11 +719,11 @@ int llmi_batch_bytes(llmi_batch* b, uint64_t* weight_bytes_per_step, uint64_t* k
     const Engine& g = *b->b.r[0];
     const uint64_t n_act = b->b.active().size();
     // the weights once; W_o (+ its int8 row scales) once more for every further active slot --
-    // unless the option "batch_attn" runs the slots' o_proj as one launch
+    // unless the option "batch_attn" or "prefix_attn" runs the slots' o_proj as one launch
     const uint64_t wo = Engine::lin_bytes(g.odt(), g.c.hidden, g.ql) + Engine::scale_bytes(g.odt(), g.c.hidden, g.ql);
+    const bool one_oproj = b->b.batch_attn || b->b.prefix_attn;
     if (weight_bytes_per_step)
-        *weight_bytes_per_step =
-            g.stream_bytes + (n_act > 1 && !b->b.batch_attn ? (n_act - 1) * wo * g.c.layers : 0);
+        *weight_bytes_per_step = g.stream_bytes + (n_act > 1 && !one_oproj ? (n_act - 1) * wo * g.c.layers : 0);
     if (kv_bytes_per_pos)
         *kv_bytes_per_pos = (uint64_t)g.c.layers * g.kvl * 2 *  // (int8 rows carry an fp16 scale)
                             (g.c.head_dim * llmi::dtype_size(g.c.kv_dtype) + (g.c.kv_dtype == LLMI_I8 ? 2 : 0));

@@ -70,6 +70,7 @@ int Engine::edit(int keep, const int32_t* ids, int n) {
     LLMI_HIP(hipGetLastError());
     if (n_val == 0) LLMI_HIP(hipStreamSynchronize(stream));  // the caller's ids were read from pageable memory
     host_next_pos = keep;
+    pfx_rows = std::min(pfx_rows, keep);  // (a batch slot: the rows from keep on are rewritten)
     prompt_len = keep + n;
     sc_m = 0;  // the logits slab holds no row of this sequence
     return LLMI_OK;

@@ -173,7 +173,22 @@ int Batch::fork(int src, const int* dst, int n_dst, int keep, const int32_t* ids
         to.push_back(r[dst[i]].get());
     }
     LLMI_REQUIRE(r[src]->prompt_len > 0, "batch fork: the source slot is idle (set_prompt first)");
-    return r[src]->fork_into(to, keep == -1 ? r[src]->host_next_pos : keep, ids, n);
+    Engine& s = *r[src];
+    const int rows = keep == -1 ? s.host_next_pos : keep;
+    LLMI_TRY(s.fork_into(to, rows, ids, n));
+    // the fork group (option prefix_attn): every destination now holds the source's rows
+    // [0, rows). A source whose group already shares at least that many keeps its group and the
+    // destinations join it; otherwise source and destinations start a group of their own. A
+    // destination leaves whatever group it was in either way.
+    if (s.pfx_group == 0 || s.pfx_rows < rows) {
+        s.pfx_group = next_group++;
+        s.pfx_rows = rows;
+    }
+    for (Engine* d : to) {
+        d->pfx_group = s.pfx_group;
+        d->pfx_rows = rows;
+    }
+    return LLMI_OK;
 }
 
 }  // namespace llmi

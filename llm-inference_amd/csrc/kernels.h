@@ -548,6 +548,42 @@ inline void oproj_batch_add(OprojBatchArgs& p, const OprojArgs& r) {
 int attn_batch_launch(const AttnBatchArgs& p, hipStream_t s);
 int oproj_batch_launch(const OprojBatchArgs& p, hipStream_t s);
 
+// ----------------- shared-prefix decode attention over forked sequence slots (attn_prefix.hip)
+// attn_batch_launch's slots, some of which are members of a fork group: every member of group g
+// holds, in its own cache, bitwise the same rows [0, rows[i]). The launch reads the group's first
+// P = min(rows) / 64 * 64 rows ONCE, from its lowest-numbered member (the leader), for all members:
+// a prefix workgroup is one (group, kv head, 64-position split below P) and serves every (member,
+// query head of the kv head) pair on the matrix cores, attn_gqa.hip's arithmetic. The splits from
+// P / 64 on of a member, and every split of a slot in no served group, are attn_body's workgroups
+// of attn_batch_launch in the same launch; the first of them seeds the slot's xacc and reports its
+// error bit. Partials go to each member's own workspace: oproj_batch_launch runs unchanged behind it.
+// A group is served if head_dim is 128, the cache f16 or i8 (16-byte aligned), heads / kv_heads <= 8,
+// direct_out 0, no granule rows, every member's nact host-sized, >= 2 members and P >= 64 (P is cut
+// to the members' (nact - 1) * 64: a prefix split never owns a position); the members of any other
+// group go through as slots of no group.
+struct AttnPrefixArgs {
+    AttnBatchArgs b;
+    int group[kAttnBatchMax] = {};  // per slot: its fork group's id, 0 = none
+    int rows[kAttnBatchMax] = {};   // per slot: the leading rows it shares with its group
+};
+constexpr int kAttnPrefixGroups = kAttnBatchMax / 2;
+struct AttnPrefixPlan {  // what the launch derives from the arguments (and hands to the kernel)
+    int n_groups = 0;    // served groups
+    int n_pfx = 0;       // prefix workgroups: the first of the grid
+    int top = 0;         // tail splits of the slot that has most
+    int skip[kAttnBatchMax] = {};    // per slot: P / 64 of its served group, its first tail split (0: none)
+    int leader[kAttnBatchMax] = {};  // per slot: the slot its prefix is read from (itself: none)
+    struct Group {
+        int n = 0, splits = 0, wg0 = 0;  // members, P / 64, first prefix workgroup
+        int member[kAttnBatchMax] = {};  // slots, ascending: member[0] is the leader
+    } g[kAttnPrefixGroups];
+};
+AttnPrefixPlan attn_prefix_plan(const AttnPrefixArgs& p);
+// true: the launch serves at least one group from its leader (else it is attn_batch_launch)
+bool attn_prefix_supported(const AttnPrefixArgs& p);
+// attn_batch_launch's errors
+int attn_prefix_launch(const AttnPrefixArgs& p, hipStream_t s);
+
 // Persistent ring layer (ring.hip): after layer l's attention, ONE launch runs
 //   o_proj (merge fused, by head) -> RMSNorm + gate_up + SiLU*up -> down (K split by CU)
 //   -> [RMSNorm + next layer's q/k/v]

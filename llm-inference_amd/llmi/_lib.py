@@ -69,7 +69,7 @@ class DebugAttnOprojArgs(C.Structure):
                 ("resid_scale", C.c_float), ("w", C.c_void_p), ("scales", C.c_void_p),
                 ("w_dtype", C.c_int), ("head_major", C.c_int), ("n_rows", C.c_int), ("ldw", C.c_int),
                 ("err", C.c_void_p), ("k_scale", C.c_void_p), ("v_scale", C.c_void_p),
-                ("gqa", C.c_int)]
+                ("gqa", C.c_int), ("prefix_group", C.c_int), ("prefix_rows", C.c_int)]
 
 
 class DebugPrefillAttnArgs(C.Structure):

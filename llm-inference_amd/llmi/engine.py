@@ -588,7 +588,9 @@ class Batch:
         attention launch; "rows_mfma" 1 runs the q/k/v, gate_up and down projections on the
         matrix cores (fp32-faithful and slot-independent, not bitwise the engine's); "batch_attn" 1
         runs the active slots' attention and their merge + o_proj as one launch each per layer
-        (W_o streamed once per step; bitwise the per-slot launches); 0 (default) off."""
+        (W_o streamed once per step; bitwise the per-slot launches); "prefix_attn" 1 lets the
+        slots of a fork group (fork / sample) read the cache rows they share once per step, from
+        one member, on the matrix cores (fp32-faithful, not bitwise); 0 (default) off."""
         call("llmi_batch_set_option", self._h, name.encode(), int(value))
 
     def edit(self, seq: int, keep: int, ids):
